@@ -4,6 +4,8 @@
     requests ranked/sec + p50 rank latency, 8k waiting queue, OPT-125m predictor.
 
     python bench.py [--gpus N --steps K --warmup W]          (N > 1: re-executes itself under torch.distributed.run)
+    python bench.py --full                                   (the whole record: see below)
+    python bench.py --dump-outputs DIR                       (scores / perm / n_selected / ran of the last timed step as .npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -25,10 +27,13 @@ gathered queue.
 * ``--trace burst|gamma``: BASELINE config 5, ranker side - replays an arrival trace through the scheduler plug-in
   (vllm_ltr_amd.replay) and prints the ranker's latency distribution per scheduler step instead of the headline line.
 
-The timed region runs with the library's event profiler OFF; the per-kernel breakdown and ``roofline`` come from a
-second pass of the same K steps with it on (``profiled_ms_per_step`` next to ``ms_per_step``).  Rank 0 prints one JSON
-line (contract in the task statement) with ``roofline`` for the dominant kernel and ``cpu_baseline`` (the oracle = CPU
-restatement of the reference, timed on this host on a bounded sample).
+A plain run sets up, runs W warm-up steps, times K steps with the library's event profiler OFF and prints one JSON line
+from rank 0 (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, the configuration).
+``--full`` adds everything else the record carries, measured after the timed steps: the per-kernel breakdown and
+``roofline`` for the dominant kernel from a second pass of the same K steps with the event profiler on
+(``profiled_ms_per_step`` next to ``ms_per_step``), the forward with separate LayerNorm launches, steady calls,
+``host_inclusive``, ``strong_scaling`` / ``scale_table``, the class head, ``config3`` and ``cpu_baseline`` (the oracle =
+CPU restatement of the reference, timed on the host's cores on a bounded sample).  Without ``--full`` those fields are null.
 """
 from __future__ import annotations
 
@@ -237,6 +242,33 @@ class ColdCall:
                 delattr(self, a)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, call):
+    """``--dump-outputs``: what the caller of the last timed step holds, one ``.npy`` per array: ``scores`` (f32 [N], the
+    predictor's score per request, in queue order), ``perm`` (the ranked order: request indices, stored as f64),
+    ``n_selected`` (length of the budget-walk prefix of ``perm``) and ``ran`` (0/1 per request: selected by the walk and
+    aged as having run).  Called right after the timed steps, before anything else touches the queue.  The inputs are
+    seeded, so two builds run with the same arguments can be compared array for array.  Above 64 MB in all, a fixed
+    seeded sample of the positions is written instead (``sample_index`` says which)."""
+    q = call.queue
+    n = call.n_total
+    torch.cuda.synchronize()
+    arrays = {"scores": q._score[:n].cpu().numpy().astype(np.float32),
+              "perm": call.perm.cpu().numpy().astype(np.float64),
+              "ran": q._out[2][:n].cpu().numpy().astype(np.float32)}
+    per_pos = sum(a.itemsize for a in arrays.values()) + 8
+    if n * per_pos > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.RandomState(0).choice(n, DUMP_MAX_BYTES // per_pos, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    arrays["n_selected"] = q._out[1].cpu().numpy().astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def run_trace(args, spec, ckpt, dev):
     """BASELINE config 5, ranker side: k arrivals -> obtain_aux_scores(k) + order + budget walk + age per scheduler step."""
     from vllm_ltr_amd.plugin import MI355XRanker
@@ -309,6 +341,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else of the record: the event-profiled second pass "
+                         "(roofline, kernels), the unfolded-LayerNorm forward, steady calls, host_inclusive, the strong-scaling "
+                         "and scale-table points, the class head, config 3 and the CPU baseline (each with its own --no-... "
+                         "switch).  Without it the run warms up, times the K steps and prints the line; those fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (scores, perm, n_selected, ran) as DIR/<name>.npy")
     ap.add_argument("--queue", type=int, default=8192, help="requests per GPU (weak scaling)")
     ap.add_argument("--queue-total", type=int, default=0,
                     help="fixed total queue at every N (strong scaling; overrides --queue)")
@@ -360,6 +399,10 @@ def main():
     ap.add_argument("--trace-cv", type=float, default=1.0)
     ap.add_argument("--trace-backbone-ms", type=float, default=25.0)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.trace or args.train):
+        ap.error("--dump-outputs writes the outputs of the cold ranker call: not with --trace / --train")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` run plainly: become the N-rank job (one process per GPU) through torch's own launcher,
@@ -502,7 +545,7 @@ def main():
     # FLOP rate is not comparable with a plain GEMM's.  For the record, time the same call once more on a second handle
     # with the fold off (LTR_F_NO_LN_FOLD at ltr_create): `roofline.unfused` below.  Outside the timed region.
     unfused = None
-    if rank == 0 and f16 and not args.no_unfused and os.environ.get("LTR_NO_LN_FOLD") != "1":
+    if args.full and rank == 0 and f16 and not args.no_unfused and os.environ.get("LTR_NO_LN_FOLD") != "1":
         sc2 = HipOPTScorer(spec, ckpt, str(dev), args.weight_dtype, chunk_tokens=args.chunk_tokens, ln_fold=False)
         tmp = torch.empty(my_r1 - my_r0, dtype=torch.float32, device=dev)
         cu_loc = np.ascontiguousarray(cu[my_r0:my_r1 + 1] - cu[my_r0]).astype(np.int32)
@@ -519,27 +562,29 @@ def main():
     # ---- the timed region: exactly K steps, event profiler OFF
     scorer.profile(False)
     elapsed, step_ms = call.timed(args.steps, 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, call)
     # ---- second pass of the same K steps with the library's event profiler on: per-class kernel time (HIP events on
     # the launch stream around every launch) for `roofline` and `kernels`
     prof, prof_elapsed = None, None
-    if not args.no_profile_pass:
+    if args.full and not args.no_profile_pass:
         scorer.profile(True)
         scorer.profile_read(reset=True)
         prof_elapsed, _ = call.timed(args.steps, 0)
         prof = scorer.profile_read(reset=True)
         scorer.profile(False)
     # rank-only latency (steady call with nothing new to score), measured outside the timed region
-    rk = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
+    rk = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20 if args.full else 0)]
     for a, b in rk:
         a.record()
         call.rank_part()
         b.record()
     torch.cuda.synchronize()
-    rank_ms = sorted(a.elapsed_time(b) for a, b in rk)
+    rank_ms = sorted(a.elapsed_time(b) for a, b in rk) or None
     # steady calls with k new requests: score the first k of the local queue on THIS GPU, then
     # promote/demote + sort + budget prefix + aging over the whole queue - what a scheduler step with k arrivals pays
     steady = {}
-    for k_new in [] if call.passive else [int(x) for x in args.steady_new.split(",") if x.strip() and int(x) > 0]:
+    for k_new in [] if call.passive or not args.full else [int(x) for x in args.steady_new.split(",") if x.strip() and int(x) > 0]:
         k_new = min(k_new, n_total)
         cu_k = np.ascontiguousarray(cu[:k_new + 1])
         ids_k, cu_k_d = call.ids_d[:int(cu_k[-1])], call.cu_d[:k_new + 1]
@@ -556,7 +601,7 @@ def main():
     # scores / order back: pinned H2D of ids + cu_seqlens, the call, pinned D2H of the scores and the order).  Reported beside
     # `value`, never as it (N = 1, outside the timed region).
     host_incl = None
-    if world == 1 and not args.sweep and not args.no_host_inclusive:
+    if args.full and world == 1 and not args.sweep and not args.no_host_inclusive:
         ids_h, cu_h = torch.from_numpy(ids).pin_memory(), torch.from_numpy(cu).pin_memory()
         sc_h = torch.empty(n_total, dtype=torch.float32).pin_memory()
         pm_h = torch.empty(n_total, dtype=torch.int32).pin_memory()
@@ -581,7 +626,7 @@ def main():
 
     # ---- north_star's strong-scaling table, the 64k point: the SAME fixed 65,536-request queue at every N
     strong_pt = None
-    if not args.no_strong and not strong and not args.sweep:
+    if args.full and not args.no_strong and not strong and not args.sweep:
         call.release()
         c64 = mk(65536)
         el, _ = c64.timed(2, 1)
@@ -592,7 +637,7 @@ def main():
     # ---- three more points of north_star's table (fixed queues of 1k / 4k / 16k requests at this N; the 8k point is the
     # headline, the 64k point `strong_scaling`): calls/s at five queue sizes in the driver's own record
     scale_pts = None
-    if not args.no_scale_points and not strong and not args.sweep:
+    if args.full and not args.no_scale_points and not strong and not args.sweep:
         if strong_pt is None:
             call.release()
         scale_pts = []
@@ -611,7 +656,7 @@ def main():
     # head of an 8,192-request call = final LayerNorm of the last-token rows + [8192, De] x [8192, De]^T logits on the
     # split-fp16 MFMA kernel + row argmax.  One-token prompts keep the forward in front of it negligible.
     class_head = None
-    if rank == 0 and world == 1 and not args.no_class_head and args.weight_dtype == "f16" and not args.sweep:
+    if args.full and rank == 0 and world == 1 and not args.no_class_head and args.weight_dtype == "f16" and not args.sweep:
         spec_c = OPTSpec.opt_125m(8192) if args.model == "125m" else OPTSpec.opt_350m(8192)
         ck = dict(ckpt)
         ck["score.weight"] = (0.05 * np.random.RandomState(1).standard_normal((8192, spec.word_embed_proj_dim))).astype(np.float16)
@@ -638,7 +683,7 @@ def main():
     # GPU - one warm-up, two timed cold calls (profiler off), one more with the event profiler for the kernel classes.  Only in
     # the default run (the headline workload on one GPU); `--model 350m --profile lmsys` is the full-length run of the same thing.
     config3 = None
-    if (rank == 0 and world == 1 and not args.no_config3 and args.weight_dtype == "f16" and not args.sweep and not strong
+    if (args.full and rank == 0 and world == 1 and not args.no_config3 and args.weight_dtype == "f16" and not args.sweep and not strong
             and (args.model, args.profile, args.queue) == ("125m", "sharegpt", 8192)):
         call.release()
         spec3 = OPTSpec.opt_350m()
@@ -765,14 +810,15 @@ def main():
                     "unfused": unfused,
                     # MFMA pipe utilisation / L2 hit rate of the kernel from the last PMC passes (profiles/gemm_pmc.json)
                     "pmc": pmc}
-        # steady rank step (nothing new to score): 37 B per request per step algorithmic (SURVEY.md 8d)
-        rk_us = rank_ms[len(rank_ms) // 2] * 1e3
         if class_head:
             kernels["class_head"] = class_head
-        kernels["rank_step"] = dict(us_per_step=rk_us, launches_per_step=2 if n_total <= 12288 else 9,
-                                    gbs=37.0 * n_total / (rk_us * 1e-6) / 1e9,
-                                    frac_hbm=37.0 * n_total / (rk_us * 1e-6) / 1e9 / PEAK_HBM_GBS,
-                                    note="latency-bound: two dependent launches over a few hundred KB")
+        # steady rank step (nothing new to score): 37 B per request per step algorithmic (SURVEY.md 8d)
+        if rank_ms:
+            rk_us = rank_ms[len(rank_ms) // 2] * 1e3
+            kernels["rank_step"] = dict(us_per_step=rk_us, launches_per_step=2 if n_total <= 12288 else 9,
+                                        gbs=37.0 * n_total / (rk_us * 1e-6) / 1e9,
+                                        frac_hbm=37.0 * n_total / (rk_us * 1e-6) / 1e9 / PEAK_HBM_GBS,
+                                        note="latency-bound: two dependent launches over a few hundred KB")
         out = {
             "metric": "requests ranked/sec (cold call: OPT predictor forward + priority sort/aging)",
             "value": n_total * args.steps / elapsed,
@@ -782,7 +828,7 @@ def main():
             "ms_per_step": elapsed / args.steps * 1e3,
             "profiled_ms_per_step": prof_elapsed / args.steps * 1e3 if prof_elapsed else None,
             "p50_rank_latency_ms": step_ms[len(step_ms) // 2],
-            "p50_steady_rank_latency_ms": rank_ms[len(rank_ms) // 2],
+            "p50_steady_rank_latency_ms": rank_ms[len(rank_ms) // 2] if rank_ms else None,
             # steady call with k new requests: score k + re-rank the whole queue (one GPU; SURVEY 8d "steady")
             "p50_steady_new_latency_ms": steady or None,
             "host_inclusive": host_incl,
@@ -817,7 +863,7 @@ def main():
             out["metric"] = ("requests ranked/sec, ONE fp16 MFMA pass per product (the reference's fp16 GPU arithmetic, ~2e-3 from "
                              "the fp32 predictor: NOT the 1e-4 headline metric)")
             out["dtype"] = "f16 weights x f16 activations (one MFMA pass), f32 accumulate"
-        if not args.no_cpu_baseline and world == 1:          # rank 0 at N = 1 only (the other ranks would idle)
+        if args.full and not args.no_cpu_baseline and world == 1:         # rank 0 at N = 1 only (the other ranks would idle)
             out["cpu_baseline"] = cpu_baseline(spec, ckpt, ids, cu, args.starv, args.period)
         print(json.dumps(out))
     if dist is not None:

@@ -380,7 +380,7 @@ def test_bench_strong_scaling_mode_two_ranks_one_device():
     env = dict(os.environ, LTR_BENCH_ONE_DEVICE="1", LTR_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--queue-total", "4096", "--no-cpu-baseline", "--no-unfused", "--steady-new", "16"]
+           "--queue-total", "4096", "--full", "--no-cpu-baseline", "--no-unfused", "--steady-new", "16"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -425,7 +425,7 @@ def test_plain_bench_gpus_2_launches_its_own_ranks():
     """`python bench.py --gpus 2` run PLAINLY - the form the driver uses - must become the 2-rank job by itself
     (re-exec under torch.distributed.run), here as a one-device dry run over gloo; the line names the ranks, the backend
     and every rank's token share; `--scale-table` adds north_star's fixed-queue table as one extra line."""
-    lines = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "1", "--queue", "2048", "--no-cpu-baseline", "--no-unfused",
+    lines = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "1", "--queue", "2048", "--full", "--no-cpu-baseline", "--no-unfused",
                          "--no-strong", "--no-scale-points", "--no-class-head", "--steady-new", "0"],
                         dict(LTR_BENCH_ONE_DEVICE="1", LTR_BENCH_BACKEND="gloo"))
     out = lines[-1]
@@ -439,7 +439,7 @@ def test_plain_bench_gpus_2_launches_its_own_ranks():
 def test_bench_driver_broadcast_two_ranks_one_device():
     """`bench.py --gpus 2 --driver-broadcast`: only rank 0 holds the queue, every timed step distributes the inputs (header +
     scatter) before the shards are scored; the line says so."""
-    lines = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "1", "--queue", "2048", "--no-cpu-baseline", "--no-unfused",
+    lines = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "1", "--queue", "2048", "--full", "--no-cpu-baseline", "--no-unfused",
                          "--no-strong", "--no-scale-points", "--no-class-head", "--steady-new", "0", "--driver-broadcast"],
                         dict(LTR_BENCH_ONE_DEVICE="1", LTR_BENCH_BACKEND="gloo"))
     out = lines[-1]
@@ -450,7 +450,7 @@ def test_bench_driver_broadcast_two_ranks_one_device():
 def test_plain_bench_gpus_1_on_rccl_world_1_with_scale_table():
     """`python bench.py --gpus 1` with LTR_BENCH_BACKEND=nccl: the process group is RCCL itself at world size 1 (init,
     barrier, the clock's MAX all-reduce, teardown), plus the scale table."""
-    lines = _bench_line(["--gpus", "1", "--steps", "1", "--warmup", "1", "--queue", "1024", "--no-cpu-baseline", "--no-unfused",
+    lines = _bench_line(["--gpus", "1", "--steps", "1", "--warmup", "1", "--queue", "1024", "--full", "--no-cpu-baseline", "--no-unfused",
                          "--no-strong", "--no-class-head", "--steady-new", "1", "--scale-table"], dict(LTR_BENCH_BACKEND="nccl"))
     table, out = lines[0], lines[-1]
     assert out["rccl_ranks"] == 1 and out["backend"] == "nccl" and out["value"] > 0
@@ -533,7 +533,7 @@ def test_world8_driver_mode_takes_both_payload_forms(form):
 def test_bench_preflight_and_payload_fallback_in_the_line():
     """`bench.py --gpus 2 --driver-broadcast` with a failing scatter: the run goes on over the broadcast form and the line says so;
     every N-rank line carries the preflight record (backend, every rank's device, a 4-byte all-gather round trip)."""
-    lines = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "1", "--queue", "2048", "--no-cpu-baseline", "--no-unfused",
+    lines = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "1", "--queue", "2048", "--full", "--no-cpu-baseline", "--no-unfused",
                          "--no-strong", "--no-scale-points", "--no-class-head", "--no-config3", "--steady-new", "0", "--driver-broadcast"],
                         dict(LTR_BENCH_ONE_DEVICE="1", LTR_BENCH_BACKEND="gloo", LTR_DIST_SCATTER_FAIL="1"))
     out = lines[-1]

@@ -59,15 +59,25 @@ def test_scores_do_not_depend_on_the_batch_size_regime(model):
         assert np.abs(want - whole[idx]).max() <= TOL
 
 
-def test_scoring_at_arrival_collects_the_same_scores():
+def test_scoring_at_arrival_collects_the_same_scores(monkeypatch):
     """``MI355XRanker(prescore=True)``: ``add_request`` starts the forward of an arrival asynchronously, the scheduler step's
     ``obtain_aux_scores`` collects.  Lone arrivals, a burst (a few growing batches), requests that never went through
     ``add_request`` and requests still waiting for a launch in one call: every request gets the score the ordinary path
-    gives it (up to the batch it was scored in: 2e-6), exactly once, in its device slot as well (the order says so)."""
+    gives it (up to the batch it was scored in: 2e-6), exactly once, in its device slot as well (the order says so).
+
+    The launch policy (``_prescore_pump``) reads the arrival times from a clock; the test gives it its own, so that the
+    arrival pattern - and with it the number of launches the bound below is about - is the same on every host: lone arrivals
+    6 ms apart (more than ``PRESCORE_BURST_S``), then 255 arrivals 10 us apart (a burst of 2.55 ms).  On the host's own clock
+    the burst took as long as its hooks did (first-use pinned allocations included), spilled over several burst windows on a
+    busy host, and the count moved with the host's load (19 launches seen against the bound of 17)."""
     import time
+    import types
     from util import FakeSeqGroup
+    from vllm_ltr_amd import prescore
     from vllm_ltr_amd.plugin import MI355XRanker
     from vllm_ltr_amd.scorer import HipOPTScorer
+    now = [100.0]
+    monkeypatch.setattr(prescore, "time", types.SimpleNamespace(perf_counter=lambda: now[0]))
     spec = OPTSpec.tiny_pre_ln()
     ckpt = seeded_checkpoint(spec, 6)
     sc = HipOPTScorer(spec, ckpt, "cuda:0", "f16")
@@ -82,8 +92,10 @@ def test_scoring_at_arrival_collects_the_same_scores():
     for g in b[:5]:                                     # lone arrivals, the engine busy in between
         rk.add_request(g)
         time.sleep(0.002)
+        now[0] += 6e-3
     for g in b[5:260]:                                  # a burst
         rk.add_request(g)
+        now[0] += 1e-5
     got = np.array(rk.obtain_aux_scores(b))             # b[260:] never saw add_request; part of the burst may still be pending
     m = rk.metrics()["prescore"]
     print("prescore:", m)

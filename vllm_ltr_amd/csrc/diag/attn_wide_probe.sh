@@ -3,7 +3,7 @@
 # the two BASELINE workloads, alternating on one box; then parity of the wide kernel.   usage: attn_wide_probe.sh <outdir>
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${1:-attn_wide}; mkdir -p $O
 cd $R
-COMMON="--no-cpu-baseline --no-unfused --no-strong --no-scale-points --no-class-head --steady-new 0"
+COMMON="--full --no-cpu-baseline --no-unfused --no-strong --no-scale-points --no-class-head --steady-new 0"
 line() { python - "$1" <<'PY'
 import json, sys
 o = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -1,4 +1,4 @@
-"""stdin: bench.py JSON line -> one short line (diagnostic helper)."""
+"""stdin: `bench.py --full` JSON line -> one short line (diagnostic helper)."""
 import json, sys
 tag = sys.argv[1] if len(sys.argv) > 1 else ""
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -34,7 +34,7 @@ cp profiles/gemm_traffic$SUF.json $O/gemm_traffic$SUF.json
 python profiles/summarize_pmc.py $(db pmc_sq) $(db pmc_l2) > $O/pmc_sq.txt 2>&1
 python profiles/make_gemm_pmc.py $(db pmc_sq) $(db pmc_l2) $O/gemm_pmc$SUF.json > /dev/null 2>&1
 cp $O/gemm_pmc$SUF.json profiles/gemm_pmc$SUF.json
-python bench.py $WL > $O/bench.json 2> $O/bench.err
+python bench.py --full $WL > $O/bench.json 2> $O/bench.err
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $O/prof -o k -- python $R/bench.py $WL --steps 2 --warmup 1 --no-cpu-baseline --no-unfused --no-profile-pass --no-strong --no-scale-points --no-class-head --no-config3 --no-host-inclusive --steady-new 0 > $O/prof.log 2>&1
 cd $R

@@ -7,7 +7,7 @@
 # bench.py --model 350m --profile lmsys, 2 steps, one box, production before and after.   usage: rln_probe.sh <outdir>
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${1:-rln_probe}; mkdir -p $O
 cd $R
-COMMON="--model 350m --profile lmsys --steps 2 --warmup 1 --no-cpu-baseline --no-unfused --no-strong --no-scale-points --no-class-head --steady-new 0"
+COMMON="--full --model 350m --profile lmsys --steps 2 --warmup 1 --no-cpu-baseline --no-unfused --no-strong --no-scale-points --no-class-head --steady-new 0"
 line() { python - "$1" <<'PY'
 import json, sys
 o = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
