@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LTR_ABI_VERSION 7
+#define LTR_ABI_VERSION 8
 
 enum {
   LTR_OK = 0,
@@ -360,6 +360,29 @@ size_t ltr_neuralndcg_workspace_bytes(int32_t B, int32_t S);
 int ltr_neuralndcg(const float* y_pred, const float* y_true, int32_t B, int32_t S, float temperature, int32_t k,
                    float pad_value, float* loss_out, float* row_ndcg_out, float* grad_out, void* workspace,
                    size_t ws_bytes, void* stream);
+
+/* Order agreement of two score vectors (ABI 8): the pair counts behind the reference's training metric, Kendall's tau
+ * (train/trainer.py:195: scipy.stats.kendalltau(labels, predictions) after every epoch), and the discordant-pair gaps by which
+ * two queue orders are compared (the orders benchmarks/benchmark_throughput_original.py:396-443 schedules by).  x, y f32 [n];
+ * every pair i < j is classified by sx = sign(x_i - x_j), sy = sign(y_i - y_j) under IEEE f32 comparison (+0 == -0, infinities
+ * are ordered):
+ *   concordant sx sy > 0; discordant sx sy < 0; tie_x sx == 0, sy != 0; tie_y sx != 0, sy == 0; tie_xy both 0; unordered: one
+ *   of the four values is a NaN.  The six counters always sum to n (n - 1) / 2.
+ *   max_gap_x / max_gap_y: max |x_i - x_j| / max |y_i - y_j| over the DISCORDANT pairs (f32 difference, fabsf);
+ *   (gap_i, gap_j): the lexicographically smallest discordant pair that attains max_gap_x.  No discordant pair: 0, 0, (-1, -1).
+ * tau-b = (C - D) / sqrt(P - tie_x - tie_xy) / sqrt(P - tie_y - tie_xy) is left to the caller (vllm_ltr_amd/metrics.py).
+ * result_out is DEVICE memory; workspace: ltr_order_agreement_workspace_bytes(n) bytes, device (0 for n < 2 and for an
+ * unsupported n).  0 <= n <= 2^20; n < 2 writes the empty result.  Anything else, a NULL pointer or a short workspace:
+ * LTR_E_INVAL, nothing launched.  Two launches on `stream`, no atomics, no memset, no host sync: bit-reproducible and safe to
+ * capture into a graph.  Launches on the current device, like ltr_rank_step. */
+typedef struct ltr_order_agreement_result {
+  int64_t concordant, discordant, tie_x, tie_y, tie_xy, unordered;
+  float   max_gap_x, max_gap_y;
+  int32_t gap_i, gap_j;
+} ltr_order_agreement_result;
+size_t ltr_order_agreement_workspace_bytes(int64_t n);
+int ltr_order_agreement(const float* x, const float* y, int32_t n, ltr_order_agreement_result* result_out,
+                        void* workspace, size_t ws_bytes, void* stream);
 
 /* The other half of SURVEY.md 8f-4: ONE optimisation step of the predictor's fine-tuning loop,
  * train/trainer.py:122-165 - forward of the OPTForSequenceClassification predictor on a slate of prompts

@@ -172,6 +172,10 @@ class HipPredictorTrainer:
 
     def predict(self, ids: np.ndarray, cu_seqlens: np.ndarray) -> np.ndarray:
         """``predictor.model.eval()`` forward with the current f32 weights (trainer.py:171-190): logits [N, num_labels]."""
+        return self.predict_device(ids, cu_seqlens).cpu().numpy()
+
+    def predict_device(self, ids: np.ndarray, cu_seqlens: np.ndarray) -> torch.Tensor:
+        """:meth:`predict` with the logits left on the device (f32 [N, num_labels])."""
         cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
         N, T = cu.shape[0] - 1, int(cu[-1])
         dev = self.device
@@ -185,7 +189,38 @@ class HipPredictorTrainer:
         _lib.check(self.lib.ltr_train_step(self._h, ids_d.data_ptr(), cu_d.data_ptr(), cu.ctypes.data, N, T, None, None, -1,
                                            None, logits.data_ptr(), self._ws.data_ptr(), self._ws.numel(), self._stream()),
                    "ltr_train_step(eval)")
-        return logits.cpu().numpy()
+        return logits
+
+    def evaluate(self, test: Sequence, batch_size: int = 32, label_max_length: int = 8192,
+                 label_group_size: int = 1) -> dict:
+        """The evaluation pass of :meth:`fit` (trainer.py:171-199) on its own, with the metric on the device: the
+        predictions of the ``test`` examples (items as in :meth:`fit`) stay in HBM and Kendall's tau-b of the labels against
+        them comes from ``metrics.order_agreement`` (``ltr_order_agreement``) instead of ``scipy.stats.kendalltau`` - the same
+        number (labels and predictions are compared as f32), without the p-value.  Returns ``kendall_tau``, the
+        ``concordant`` / ``discordant`` / ``pairs`` counts behind it and, for crossentropy, ``acc`` as :meth:`fit` computes it."""
+        from .metrics import order_agreement
+        from .scorer import HipOPTScorer
+        preds, classes, train_labels = [], [], []
+        for b0 in range(0, len(test), batch_size):
+            chunk = test[b0:b0 + batch_size]
+            ids, cu = HipOPTScorer.pack([t[0] for t in chunk])
+            out = self.predict_device(ids, cu)
+            if self.loss == "crossentropy":                                                                      # :186-187
+                classes.extend(out.cpu().numpy().argmax(-1).tolist())
+            else:
+                preds.append(out[:, 0])                                                                          # :188-189
+            train_labels.extend(len2label(t[2], label_max_length, label_group_size) if len(t) > 2 else t[1]
+                                for t in chunk)                                                                  # :191
+        truth = torch.tensor([float(t[1]) for t in test], dtype=torch.float32, device=self.device)              # :190
+        if self.loss == "crossentropy":
+            pred = torch.tensor(classes, dtype=torch.float32, device=self.device)
+        else:
+            pred = torch.cat(preds) if preds else torch.empty(0, dtype=torch.float32, device=self.device)
+        r = order_agreement(truth, pred)                                                                         # :195
+        rec = dict(kendall_tau=r.tau_b, concordant=r.concordant, discordant=r.discordant, pairs=r.pairs)
+        if self.loss == "crossentropy":
+            rec["acc"] = float((np.asarray(train_labels) == np.asarray(classes)).mean())                      # :198-199
+        return rec
 
     def fit(self, train: Sequence, test: Sequence, epochs: int = 1, batch_size: int = 32, seed: int = 42,
             log=print, label_max_length: int = 8192, label_group_size: int = 1) -> List[dict]:
