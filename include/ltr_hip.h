@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LTR_ABI_VERSION 8
+#define LTR_ABI_VERSION 9
 
 enum {
   LTR_OK = 0,
@@ -278,6 +278,25 @@ int ltr_head_destroy(ltr_head_handle h);
  * the index_select of opt.py:252-254); scores_out f32 [N]. */
 int ltr_head_score(ltr_head_handle h, const float* hidden, const int32_t* row_index, int32_t N,
                    float* scores_out, void* stream);
+/* The same head on a batch of rows in the backbone's own dtype, on the matrix cores (ABI 9): what
+ * OPTDecoder.forward hands the predictor - (residual + hidden_states).index_select(0, selected_token_indices),
+ * vllm/model_executor/models/opt.py:250-255 - in the dtype the head was created under (set_default_torch_dtype(
+ * model_config.dtype), model_loader/loader.py:234-241).
+ *   hidden        [rows, n_features] of hidden_dtype (LTR_HID_*), row-major
+ *   residual      NULL, or the same dtype and shape: the rows scored are hidden + residual, the sum formed in f32 and rounded
+ *                 once to hidden_dtype (the reference's tensor add; no rounding for f32)
+ *   row_index     int32 [N] or NULL (rows 0..N-1)
+ *   workspace     ltr_head_workspace_bytes(h, N) bytes of device memory, the caller's (short: LTR_E_NOMEM)
+ * Needs LTR_W_F16 weights (exact in fp16); an LTR_W_F32 handle is refused with LTR_E_INVAL - score it with ltr_head_score.
+ * A NULL pointer or a bad dtype: LTR_E_INVAL.  N == 0: LTR_OK.  Two launches per dense layer on `stream`; nothing is
+ * allocated, no atomics, no memset, no function attribute is set: safe under stream capture, and a row's score does not
+ * depend on the batch it is scored in (bit for bit). */
+enum { LTR_HID_F32 = 0, LTR_HID_F16 = 1, LTR_HID_BF16 = 2 };
+/* reference: the predictor's inputs have no counterpart of this (torch allocates); bytes for N rows, 0 for N <= 0 */
+size_t ltr_head_workspace_bytes(ltr_head_handle h, int32_t N);
+int ltr_head_score_batched(ltr_head_handle h, const void* hidden, const void* residual /* NULL | same dtype and shape */,
+                           int32_t hidden_dtype, const int32_t* row_index, int32_t N, float* scores_out,
+                           void* workspace, size_t ws_bytes, void* stream);
 
 /* Per-kernel-class timing for the roofline report (bench.py).  When enabled, ltr_score /
  * ltr_forward_hidden bracket every launch with HIP events on the caller's stream (no host

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("LTR_LIB") or os.path.join(_HERE, "csrc", "libltr_hip.
 
 LTR_W_F32, LTR_W_F16 = 0, 1
 LTR_WS_SCORE, LTR_WS_RANK = 0, 1
+LTR_HID_F32, LTR_HID_F16, LTR_HID_BF16 = 0, 1, 2
 LTR_RANK_USE_PRI, LTR_RANK_ASCENDING = 1, 2
 LTR_WT_GLOBAL_COUNT, LTR_WL_COUNT = 7, 12
 
@@ -23,15 +24,16 @@ LTR_WT_GLOBAL_COUNT, LTR_WL_COUNT = 7, 12
 SYMBOLS = ("ltr_abi_version", "ltr_last_error", "ltr_create", "ltr_destroy", "ltr_workspace_bytes",
            "ltr_set_chunk_tokens", "ltr_score", "ltr_forward_hidden", "ltr_embed_gather", "ltr_pool_head",
            "ltr_rank_step", "ltr_age_update", "ltr_budget_prefix", "ltr_profile_enable", "ltr_profile_read",
-           "ltr_head_create", "ltr_head_destroy", "ltr_head_score", "ltr_reserve_select", "ltr_listmle",
+           "ltr_head_create", "ltr_head_destroy", "ltr_head_score", "ltr_head_score_batched", "ltr_head_workspace_bytes",
+           "ltr_reserve_select", "ltr_listmle",
            "ltr_neuralndcg", "ltr_neuralndcg_workspace_bytes", "ltr_order_agreement", "ltr_order_agreement_workspace_bytes",
            "ltr_status", "ltr_queue_step", "ltr_train_create", "ltr_train_destroy", "ltr_train_workspace_bytes",
            "ltr_train_step", "ltr_train_read", "ltr_attention", "ltr_train_attention",
            "ltr_train_attention_workspace_bytes")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
-LTR_E_INVAL, LTR_E_RANGE = -22, -34
+LTR_E_INVAL, LTR_E_RANGE, LTR_E_NOMEM = -22, -34, -12
 
 
 class LtrError(RuntimeError):
@@ -138,6 +140,9 @@ def _load() -> C.CDLL:
     lib.ltr_head_create.argtypes = [C.POINTER(HeadDesc), C.POINTER(vp), i32, C.POINTER(vp)]
     lib.ltr_head_destroy.argtypes = [vp]
     lib.ltr_head_score.argtypes = [vp, vp, vp, i32, vp, vp]
+    lib.ltr_head_workspace_bytes.argtypes = [vp, i32]
+    lib.ltr_head_workspace_bytes.restype = sz
+    lib.ltr_head_score_batched.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, sz, vp]
     lib.ltr_train_create.argtypes = [C.POINTER(ModelDesc), C.POINTER(vp), i32, C.POINTER(TrainConfig), vp, C.POINTER(vp)]
     lib.ltr_train_destroy.argtypes = [vp]
     lib.ltr_train_workspace_bytes.argtypes = [vp, i64, i64]
@@ -151,7 +156,7 @@ def _load() -> C.CDLL:
         fn = getattr(lib, name)
         if name not in ("ltr_last_error", "ltr_workspace_bytes", "ltr_abi_version", "ltr_train_workspace_bytes",
                         "ltr_train_attention_workspace_bytes", "ltr_neuralndcg_workspace_bytes",
-                        "ltr_order_agreement_workspace_bytes"):
+                        "ltr_order_agreement_workspace_bytes", "ltr_head_workspace_bytes"):
             fn.restype = C.c_int
     if lib.ltr_abi_version() != ABI_VERSION:
         raise LtrError(f"{LIB_PATH} has ABI version {lib.ltr_abi_version()}, this binding needs {ABI_VERSION}: rebuild")

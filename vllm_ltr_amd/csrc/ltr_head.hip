@@ -17,29 +17,9 @@ namespace {
 constexpr int HD_THREADS = 256;
 constexpr int HD_MAXW = 8192;     // widest vector kept in LDS
 
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2, ACT_TANH = 3, ACT_GELU = 4, ACT_SILU = 5 };
-
-__device__ __forceinline__ float apply_act(float x, int act) {
-  switch (act) {
-    case ACT_RELU: return fmaxf(x, 0.f);
-    case ACT_SIGMOID: return 1.f / (1.f + expf(-x));
-    case ACT_TANH: return tanhf(x);
-    case ACT_GELU: return 0.5f * x * (1.f + erff(x * 0.70710678118654752f));   // nn.GELU default (erf)
-    case ACT_SILU: return x / (1.f + expf(-x));
-    default: return x;
-  }
-}
-
 template <typename WT> __device__ __forceinline__ float wl(const WT* p);
 template <> __device__ __forceinline__ float wl<float>(const float* p) { return *p; }
 template <> __device__ __forceinline__ float wl<__half>(const __half* p) { return __half2float(*p); }
-
-struct HeadLayers {
-  const void* w[10];       // up to 8 FC layers + output layer
-  const float* b[10];
-  int in[10], out[10];
-  int n;                   // number of dense layers including the output layer
-};
 
 template <typename WT>
 __global__ void __launch_bounds__(HD_THREADS) ltr_head_kernel(const float* __restrict__ hidden,
@@ -97,15 +77,6 @@ __global__ void __launch_bounds__(HD_THREADS) ltr_head_kernel(const float* __res
 }
 
 }  // namespace
-
-struct HeadModel {
-  ltr_head_desc d;
-  HeadLayers L;
-  const float* ln_w;
-  const float* ln_b;
-  int maxw;
-};
-
 }  // namespace ltr
 
 using namespace ltr;

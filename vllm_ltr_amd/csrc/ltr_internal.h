@@ -243,6 +243,35 @@ __device__ __forceinline__ void split_f16(float a, __half& hi, __half& lo) {
   lo = __float2half_rn(a - __half2float(hi));
 }
 
+// ---- hidden-state head (ltr_head.hip: row kernel; ltr_head_mfma.hip: batched MFMA path) ------------
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2, ACT_TANH = 3, ACT_GELU = 4, ACT_SILU = 5 };
+
+__device__ __forceinline__ float apply_act(float x, int act) {
+  switch (act) {
+    case ACT_RELU: return fmaxf(x, 0.f);
+    case ACT_SIGMOID: return 1.f / (1.f + expf(-x));
+    case ACT_TANH: return tanhf(x);
+    case ACT_GELU: return 0.5f * x * (1.f + erff(x * 0.70710678118654752f));   // nn.GELU default (erf)
+    case ACT_SILU: return x / (1.f + expf(-x));
+    default: return x;
+  }
+}
+
+struct HeadLayers {
+  const void* w[10];       // up to 8 FC layers + output layer
+  const float* b[10];
+  int in[10], out[10];
+  int n;                   // number of dense layers including the output layer
+};
+
+struct HeadModel {
+  ltr_head_desc d;
+  HeadLayers L;
+  const float* ln_w;
+  const float* ln_b;
+  int maxw;
+};
+
 // largest i in [0, n) with cu[i] <= t   (cu ascending, cu[0] <= t < cu[n])
 __device__ __forceinline__ int find_request(const int32_t* __restrict__ cu, int n, int t) {
   int lo = 0, hi = n;  // answer in [lo, hi)

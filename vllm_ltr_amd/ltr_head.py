@@ -33,6 +33,8 @@ class HipLTRHead:
             t += [mat(state[f"input_layer.layers.{i}.weight"]), f32(state[f"input_layer.layers.{i}.bias"])]
         t += [mat(state["output_layer.w_1.weight"]), f32(state["output_layer.w_1.bias"])]
         self._tensors = t
+        self.n_features = n_features
+        self._ws = None                      # workspace of the batched path: grows, never shrinks
         desc = _lib.HeadDesc()
         desc.n_features, desc.n_fc = n_features, len(sizes)
         for i, s in enumerate(sizes):
@@ -54,13 +56,49 @@ class HipLTRHead:
         except Exception:
             pass
 
-    def score(self, hidden: torch.Tensor, row_index: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """hidden f32 [rows, n_features] on the device; row_index int32 [N] or None."""
-        assert hidden.dtype == torch.float32 and hidden.is_cuda and hidden.is_contiguous()
+    _HID = {torch.float32: _lib.LTR_HID_F32, torch.float16: _lib.LTR_HID_F16, torch.bfloat16: _lib.LTR_HID_BF16}
+
+    def reserve(self, n: int) -> None:
+        """Size the batched path's workspace for calls of up to ``n`` rows (it only grows; do it before a graph capture)."""
+        need = int(self.lib.ltr_head_workspace_bytes(self._h, n))
+        if self._ws is None or self._ws.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.LtrError(f"HipLTRHead: the workspace must grow to {need} bytes for {n} rows while the stream is "
+                                    "capturing; call reserve(n) before the capture")
+            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+
+    def score(self, hidden: torch.Tensor, row_index: Optional[torch.Tensor] = None,
+              residual: Optional[torch.Tensor] = None, batched: Optional[bool] = None) -> torch.Tensor:
+        """hidden f32 / fp16 / bf16 [rows, n_features] on the device; row_index int32 (or int64) [N] or None; residual None or a
+        tensor like hidden (the rows scored are ``residual + hidden`` in hidden's dtype, opt.py:250-255).
+
+        f32 hidden without residual runs the row kernel (``ltr_head_score``) unless ``batched=True``; fp16 / bf16 hidden
+        or a residual run the batched MFMA path (``ltr_head_score_batched``), which ``batched=False`` therefore refuses."""
+        assert hidden.is_cuda and hidden.is_contiguous() and hidden.dim() == 2 and hidden.shape[1] == self.n_features
+        if hidden.dtype not in self._HID:
+            raise ValueError(f"HipLTRHead.score: hidden dtype {hidden.dtype} (float32, float16 or bfloat16)")
+        if row_index is not None and row_index.dtype != torch.int32:
+            row_index = row_index.to(torch.int32)              # selected_token_indices arrives as int64
         n = hidden.shape[0] if row_index is None else row_index.numel()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        idx = row_index.data_ptr() if row_index is not None else None
+        if batched is None:
+            batched = hidden.dtype != torch.float32 or residual is not None
+        if not batched:
+            if hidden.dtype != torch.float32 or residual is not None:
+                raise ValueError("HipLTRHead.score: batched=False is the f32 row kernel; it takes no fp16 / bf16 hidden "
+                                 "and no residual")
+            out = torch.empty(n, dtype=torch.float32, device=self.device)
+            _lib.check(self.lib.ltr_head_score(self._h, hidden.data_ptr(), idx, n, out.data_ptr(), stream), "ltr_head_score")
+            return out
+        if residual is not None:
+            assert residual.is_cuda and residual.is_contiguous()
+            if residual.dtype != hidden.dtype or residual.shape != hidden.shape:
+                raise ValueError("HipLTRHead.score: residual must have hidden's dtype and shape")
+        self.reserve(n)
         out = torch.empty(n, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.ltr_head_score(self._h, hidden.data_ptr(),
-                                           row_index.data_ptr() if row_index is not None else None, n,
-                                           out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
-                   "ltr_head_score")
+        _lib.check(self.lib.ltr_head_score_batched(self._h, hidden.data_ptr(),
+                                                   residual.data_ptr() if residual is not None else None,
+                                                   self._HID[hidden.dtype], idx, n, out.data_ptr(), self._ws.data_ptr(),
+                                                   self._ws.numel(), stream), "ltr_head_score_batched")
         return out
