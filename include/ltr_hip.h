@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LTR_ABI_VERSION 9
+#define LTR_ABI_VERSION 10
 
 enum {
   LTR_OK = 0,
@@ -451,6 +451,55 @@ int ltr_train_step(ltr_train_handle h, const int64_t* token_ids, const int32_t* 
  * dst (device, f32, `capacity` floats) on `stream`; *count_out = its element count (dst NULL: size query). */
 int ltr_train_read(ltr_train_handle h, int32_t index, int32_t what, float* dst, size_t capacity,
                    size_t* count_out, void* stream);
+
+/* Training of the hidden-state head on the device (ABI 10; DESIGN.md 4.4 "training").  The reference only Xavier-initialises
+ * the head (vllm/model_executor/predictor.py:126-145); its model class is the encoder-less copy of allRank's FCModel /
+ * OutputLayer / LTRModel (train/allrank/models/model.py:28-166), which allRank's loop trains
+ * (train/allrank/training/train_utils.py:34-45: loss, backward, clip_grad_norm_, opt.step).  One call is one such step on
+ * M = B * S selected rows of stored hidden states: forward (gather, residual and input LayerNorm as in ltr_head_score_batched),
+ * the loss on the [B, S] scores, backward and torch.optim.Adam.  Parameters, gradients and moments are f32 and library-owned;
+ * every product runs on v_mfma_f32_16x16x32_f16 with BOTH operands split into fp16 hi + lo (f32-grade products, f32
+ * accumulation in a fixed order).  No atomics, no memset, no allocation in a step, every dependency is a launch boundary:
+ * two trainers fed the same slates hold bit-identical parameters.
+ * NOT built: dropout (FCModel's nn.Dropout, model.py:45-66 - a head with dropout is outside this interface), the gradient
+ * w.r.t. `hidden`, and stream capture of a step (Adam's bias corrections are host-side arguments of a launch). */
+enum { LTR_HEAD_LOSS_GIVEN = 4 };   /* y_true holds dLoss/dscore [B, S] (a loss computed elsewhere); loss_out is not touched */
+typedef struct ltr_head_train_config {
+  float lr, beta1, beta2, eps, weight_decay;   /* torch.optim.Adam (train_utils.py:34-45 steps the optimizer it is handed) */
+  int32_t loss;          /* LTR_LOSS_LISTMLE | LTR_LOSS_MSE | LTR_LOSS_NEURALNDCG | LTR_HEAD_LOSS_GIVEN; LTR_LOSS_CROSSENTROPY: LTR_E_INVAL */
+  float listmle_eps;     /* allrank DEFAULT_EPS 1e-10 */
+  float pad_value;       /* allrank PADDED_Y_VALUE -1 */
+  float clip_norm;       /* clip_grad_norm_ (train_utils.py:40-41); <= 0: off */
+} ltr_head_train_config;
+typedef struct ltr_head_trainer* ltr_head_train_handle;
+/* replaces predictor_model's construction + the optimizer's state (predictor.py:126-145): COPIES the f32 weights - pointer
+ * order of the scoring head's create call, every tensor f32, desc.weight_dtype must be LTR_W_F32 - into library-owned
+ * parameter / gradient / moment buffers and builds the fp16 hi | lo images of every matrix and of its transpose on `stream`,
+ * which it synchronises. */
+int ltr_head_train_create(const ltr_head_desc* desc, const void* const* weights_f32, int32_t n_weights,
+                          const ltr_head_train_config* cfg, void* stream, ltr_head_train_handle* out);
+int ltr_head_train_destroy(ltr_head_train_handle h);
+/* reference: no counterpart (torch allocates activations and gradients); bytes for a [B, S] slate, 0 for B * S <= 0 */
+size_t ltr_head_train_workspace_bytes(ltr_head_train_handle h, int32_t B, int32_t S);
+/* One step of train_utils.py:34-45 on a slate.
+ *   hidden / residual / hidden_dtype / row_index   as in ltr_head_score_batched; row_index int32 [B * S] or NULL
+ *   y_true    f32 [B, S] labels (items equal to pad_value are masked by listMLE / neuralNDCG; MSE is torch's MSELoss: the mean
+ *             over all B * S, nothing masked), or dLoss/dscore under LTR_HEAD_LOSS_GIVEN
+ *   shuffle   int32 [S], listMLE only (the permutation of losses/listMLE.py:33)
+ *   apply_update 1: the step; 0: gradients only (moments and step count stay)
+ *   loss_out f32 [1]; scores_out f32 [B, S] or NULL: the scores BEFORE the update; grad_norm_out f32 [1] or NULL: the
+ *   global L2 norm of all gradients before clipping.  All device memory.
+ * Argument errors (NULL pointer, bad dtype, neuralNDCG outside 2 <= S <= 1024, listMLE without shuffle or S > 4096):
+ * LTR_E_INVAL; short workspace: LTR_E_NOMEM; nothing is launched.  B * S == 0: LTR_OK. */
+int ltr_head_train_step(ltr_head_train_handle h, const void* hidden, const void* residual, int32_t hidden_dtype,
+                        const int32_t* row_index, int32_t B, int32_t S, const float* y_true, const int32_t* shuffle,
+                        int32_t apply_update, float* loss_out, float* scores_out, float* grad_norm_out, void* workspace,
+                        size_t ws_bytes, void* stream);
+/* Copies parameter (what = 0) or gradient of the last step, after clipping (what = 1), tensor `index` (the create call's
+ * pointer order) into dst (device, f32, `capacity` floats) on `stream`; *count_out = its element count (dst NULL: size query).
+ * What a torch user reads from model.state_dict() / p.grad. */
+int ltr_head_train_read(ltr_head_train_handle h, int32_t index, int32_t what, float* dst, size_t capacity,
+                        size_t* count_out, void* stream);
 
 /* The attention block of the training step ALONE, forward + backward, on the kernels ltr_train_step runs (split-fp16
  * MFMA; what autograd does for OPTAttention in train/trainer.py:147-159): for every request r and head,

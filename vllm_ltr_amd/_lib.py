@@ -29,8 +29,9 @@ SYMBOLS = ("ltr_abi_version", "ltr_last_error", "ltr_create", "ltr_destroy", "lt
            "ltr_neuralndcg", "ltr_neuralndcg_workspace_bytes", "ltr_order_agreement", "ltr_order_agreement_workspace_bytes",
            "ltr_status", "ltr_queue_step", "ltr_train_create", "ltr_train_destroy", "ltr_train_workspace_bytes",
            "ltr_train_step", "ltr_train_read", "ltr_attention", "ltr_train_attention",
-           "ltr_train_attention_workspace_bytes")
-ABI_VERSION = 9
+           "ltr_train_attention_workspace_bytes", "ltr_head_train_create", "ltr_head_train_destroy",
+           "ltr_head_train_workspace_bytes", "ltr_head_train_step", "ltr_head_train_read")
+ABI_VERSION = 10
 
 
 LTR_E_INVAL, LTR_E_RANGE, LTR_E_NOMEM = -22, -34, -12
@@ -68,6 +69,14 @@ class TrainConfig(C.Structure):
                 ("dropout", C.c_float), ("precision", C.c_int32), ("seed", C.c_uint64)]
 
 
+class HeadTrainConfig(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("weight_decay", C.c_float), ("loss", C.c_int32), ("listmle_eps", C.c_float), ("pad_value", C.c_float),
+                ("clip_norm", C.c_float)]
+
+
+LTR_HEAD_LOSS_GIVEN = 4
+HEAD_LOSSES = {"listMLE": 0, "mse": 1, "neuralNDCG": 3, "given": LTR_HEAD_LOSS_GIVEN}
 LOSSES = {"listMLE": 0, "mse": 1, "crossentropy": 2, "neuralNDCG": 3}
 TRAIN_PRECISIONS = {None: 0, "split": 1, "f32": 2}
 
@@ -143,6 +152,12 @@ def _load() -> C.CDLL:
     lib.ltr_head_workspace_bytes.argtypes = [vp, i32]
     lib.ltr_head_workspace_bytes.restype = sz
     lib.ltr_head_score_batched.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, sz, vp]
+    lib.ltr_head_train_create.argtypes = [C.POINTER(HeadDesc), C.POINTER(vp), i32, C.POINTER(HeadTrainConfig), vp, C.POINTER(vp)]
+    lib.ltr_head_train_destroy.argtypes = [vp]
+    lib.ltr_head_train_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.ltr_head_train_workspace_bytes.restype = sz
+    lib.ltr_head_train_step.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]
+    lib.ltr_head_train_read.argtypes = [vp, i32, i32, vp, sz, C.POINTER(sz), vp]
     lib.ltr_train_create.argtypes = [C.POINTER(ModelDesc), C.POINTER(vp), i32, C.POINTER(TrainConfig), vp, C.POINTER(vp)]
     lib.ltr_train_destroy.argtypes = [vp]
     lib.ltr_train_workspace_bytes.argtypes = [vp, i64, i64]
@@ -156,7 +171,8 @@ def _load() -> C.CDLL:
         fn = getattr(lib, name)
         if name not in ("ltr_last_error", "ltr_workspace_bytes", "ltr_abi_version", "ltr_train_workspace_bytes",
                         "ltr_train_attention_workspace_bytes", "ltr_neuralndcg_workspace_bytes",
-                        "ltr_order_agreement_workspace_bytes", "ltr_head_workspace_bytes"):
+                        "ltr_order_agreement_workspace_bytes", "ltr_head_workspace_bytes",
+                        "ltr_head_train_workspace_bytes"):
             fn.restype = C.c_int
     if lib.ltr_abi_version() != ABI_VERSION:
         raise LtrError(f"{LIB_PATH} has ABI version {lib.ltr_abi_version()}, this binding needs {ABI_VERSION}: rebuild")

@@ -25,62 +25,12 @@ namespace {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-struct bf16_t { uint16_t u; };
-
 constexpr int HB_THREADS = 256;
 constexpr int HB_BM = 64, HB_BN = 64, HB_BK = 64;   // tile of a workgroup; 4 waves as 2 x 2, 32 x 32 outputs each
 constexpr int HB_LD = HB_BK + 8;                    // halves per LDS row: 144 B, the 16-B fragment reads of 8 rows hit 32 different banks
 constexpr int HB_PLANE = HB_BM * HB_LD;             // halves per plane (X hi, X lo, W)
 constexpr int HB_CLD = HB_BN + 1;                   // floats per row of the output layer's score tile
 static_assert(3 * HB_PLANE * 2 >= HB_BM * HB_CLD * 4, "the score tile reuses the operand planes");
-
-template <typename T> __device__ __forceinline__ float widen(T v);
-template <> __device__ __forceinline__ float widen<float>(float v) { return v; }
-template <> __device__ __forceinline__ float widen<__half>(__half v) { return __half2float(v); }
-template <> __device__ __forceinline__ float widen<bf16_t>(bf16_t v) { return __uint_as_float((uint32_t)v.u << 16); }
-
-// f32 sum rounded once to the tensor's dtype (what `residual + hidden_states` holds in the reference)
-template <typename T> __device__ __forceinline__ float round_to(float s);
-template <> __device__ __forceinline__ float round_to<float>(float s) { return s; }
-template <> __device__ __forceinline__ float round_to<__half>(float s) { return __half2float(__float2half_rn(s)); }
-template <> __device__ __forceinline__ float round_to<bf16_t>(float s) {
-  uint32_t u = __float_as_uint(s);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return s;     // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                   // round to nearest even
-  return __uint_as_float(u & 0xffff0000u);
-}
-
-// o[0..4) = row[c .. c + 4) widened, 0 beyond K.  VEC: K is a multiple of 16 and the row is 16-byte aligned, so a group
-// of four that starts inside the row lies inside it and is one aligned load.
-template <typename T, bool VEC> __device__ __forceinline__ void load4(const T* __restrict__ row, int c, int K, float o[4]) {
-  if (VEC) {
-    if (c >= K) { o[0] = o[1] = o[2] = o[3] = 0.f; return; }
-    if constexpr (sizeof(T) == 4) {
-      const float4 v = *reinterpret_cast<const float4*>(row + c);
-      o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-    } else {
-      const uint2 v = *reinterpret_cast<const uint2*>(row + c);
-      T e[4];
-      __builtin_memcpy(e, &v, 8);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) o[i] = widen<T>(e[i]);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = c + i < K ? widen<T>(row[c + i]) : 0.f;
-  }
-}
-
-template <typename T, bool VEC>
-__device__ __forceinline__ void load_x4(const T* __restrict__ xr, const T* __restrict__ rr, int c, int K, float o[4]) {
-  load4<T, VEC>(xr, c, K, o);
-  if (rr != nullptr) {
-    float r[4];
-    load4<T, VEC>(rr, c, K, r);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = round_to<T>(o[i] + r[i]);
-  }
-}
 
 // stats[r] = (mean, rstd, 1) with norm, (0, 1, split_scale(max|x|)) without; one wave per row, lanes own groups of four
 template <typename T, bool VEC>
