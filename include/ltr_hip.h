@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LTR_ABI_VERSION 10
+#define LTR_ABI_VERSION 11
 
 enum {
   LTR_OK = 0,
@@ -297,6 +297,42 @@ size_t ltr_head_workspace_bytes(ltr_head_handle h, int32_t N);
 int ltr_head_score_batched(ltr_head_handle h, const void* hidden, const void* residual /* NULL | same dtype and shape */,
                            int32_t hidden_dtype, const int32_t* row_index, int32_t N, float* scores_out,
                            void* workspace, size_t ws_bytes, void* stream);
+
+/* Slate encoder of the head (ABI 11; DESIGN.md 4.4 "slate encoder"): allRank's Transformer encoder between the FC stack and
+ * the output layer - train/allrank/models/transformer.py:44-263, wired by model.py:147-161 from ModelConfig.transformer
+ * (config_predictor.py:8-38).  Scoring only (dropout is the identity).  The rows of a call are grouped into B unpadded
+ * slates; attention is not causal and stays inside a slate, so there is no padding mask.  Per block
+ * z += MHA(norm(z)); z += w_2(relu(w_1(norm(z)))) with allRank's LayerNorm (unbiased std, eps = 1e-6 added to std), then
+ * the encoder's final norm and the head's output layer.  d_model is the width of the head's last FC layer (n_features
+ * without one) and must be >= 2; d_k = d_model / h must be a multiple of 16 up to 128; positional_encoding must be 0 (not
+ * built: a queue has no item order to encode); the head must hold LTR_W_F16 weights.  Anything else: LTR_E_INVAL.
+ * Weight pointers, 12 per block then 2: sublayer.0.norm.a_2, .b_2 (f32 [d_model]); the stacked self_attn.linears.0 | 1 | 2
+ * weight fp16 [3 d_model, d_model] and bias f32 [3 d_model]; linears.3 weight fp16, bias f32; sublayer.1.norm.a_2, .b_2;
+ * feed_forward.w_1 weight fp16 [d_ff, d_model], bias; w_2 weight fp16 [d_model, d_ff], bias; at the end encoder.norm.a_2,
+ * .b_2.  The encoder borrows the head and the weights: both must outlive it.  Create touches no device. */
+typedef struct ltr_head_encoder_desc {
+  int32_t n_blocks;             /* TransformerConfig.N, 1 .. 16 */
+  int32_t d_ff;
+  int32_t h;
+  int32_t positional_encoding;  /* 0: null */
+} ltr_head_encoder_desc;
+typedef struct ltr_head_encoder* ltr_head_encoder_handle;
+int ltr_head_encoder_create(ltr_head_handle head, const ltr_head_encoder_desc* desc, const void* const* weights,
+                            int32_t n_weights, ltr_head_encoder_handle* out);
+int ltr_head_encoder_destroy(ltr_head_encoder_handle enc);
+size_t ltr_head_encoder_workspace_bytes(ltr_head_encoder_handle enc, int32_t N);
+/* hidden / residual / hidden_dtype / row_index / N / workspace as in ltr_head_score_batched.
+ *   cu_slates  int32 [B + 1] on the device, ascending, cu_slates[0] = 0, cu_slates[B] = N (the cu_seqlens idiom of
+ *              ltr_score); an empty slate contributes nothing; NULL with B = 1: the call is one slate.  The host cannot see
+ *              it: the kernel clamps it into [0, N], so a malformed array gives wrong scores but touches no other memory.
+ *   max_slate  the longest slate; it sizes the attention grid and nothing else.  A workgroup strides over the query tiles
+ *              of its slate, so a value that is too small costs time and never a score; <= 0 or > N means N.
+ * 5 dense layers (2 launches each) and one attention launch per block on `stream`; nothing is allocated, no atomics, no
+ * memset, no function attribute: safe under stream capture.  A slate's scores do not depend on the other slates of the
+ * call (bit for bit). */
+int ltr_head_encoder_score(ltr_head_encoder_handle enc, const void* hidden, const void* residual, int32_t hidden_dtype,
+                           const int32_t* row_index, int32_t N, const int32_t* cu_slates, int32_t B, int32_t max_slate,
+                           float* scores_out, void* workspace, size_t ws_bytes, void* stream);
 
 /* Per-kernel-class timing for the roofline report (bench.py).  When enabled, ltr_score /
  * ltr_forward_hidden bracket every launch with HIP events on the caller's stream (no host

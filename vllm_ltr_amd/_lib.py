@@ -30,8 +30,10 @@ SYMBOLS = ("ltr_abi_version", "ltr_last_error", "ltr_create", "ltr_destroy", "lt
            "ltr_status", "ltr_queue_step", "ltr_train_create", "ltr_train_destroy", "ltr_train_workspace_bytes",
            "ltr_train_step", "ltr_train_read", "ltr_attention", "ltr_train_attention",
            "ltr_train_attention_workspace_bytes", "ltr_head_train_create", "ltr_head_train_destroy",
-           "ltr_head_train_workspace_bytes", "ltr_head_train_step", "ltr_head_train_read")
-ABI_VERSION = 10
+           "ltr_head_train_workspace_bytes", "ltr_head_train_step", "ltr_head_train_read",
+           "ltr_head_encoder_create", "ltr_head_encoder_destroy", "ltr_head_encoder_workspace_bytes",
+           "ltr_head_encoder_score")
+ABI_VERSION = 11
 
 
 LTR_E_INVAL, LTR_E_RANGE, LTR_E_NOMEM = -22, -34, -12
@@ -58,6 +60,10 @@ class HeadDesc(C.Structure):
     _fields_ = [("n_features", C.c_int32), ("n_fc", C.c_int32), ("fc_sizes", C.c_int32 * 8),
                 ("input_norm", C.c_int32), ("activation", C.c_int32), ("d_output", C.c_int32),
                 ("output_activation", C.c_int32), ("weight_dtype", C.c_int32)]
+
+
+class HeadEncoderDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_blocks", "d_ff", "h", "positional_encoding")]
 
 
 ACTIVATIONS = {None: 0, "Identity": 0, "ReLU": 1, "Sigmoid": 2, "Tanh": 3, "GELU": 4, "SiLU": 5}
@@ -152,6 +158,11 @@ def _load() -> C.CDLL:
     lib.ltr_head_workspace_bytes.argtypes = [vp, i32]
     lib.ltr_head_workspace_bytes.restype = sz
     lib.ltr_head_score_batched.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, sz, vp]
+    lib.ltr_head_encoder_create.argtypes = [vp, C.POINTER(HeadEncoderDesc), C.POINTER(vp), i32, C.POINTER(vp)]
+    lib.ltr_head_encoder_destroy.argtypes = [vp]
+    lib.ltr_head_encoder_workspace_bytes.argtypes = [vp, i32]
+    lib.ltr_head_encoder_workspace_bytes.restype = sz
+    lib.ltr_head_encoder_score.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, sz, vp]
     lib.ltr_head_train_create.argtypes = [C.POINTER(HeadDesc), C.POINTER(vp), i32, C.POINTER(HeadTrainConfig), vp, C.POINTER(vp)]
     lib.ltr_head_train_destroy.argtypes = [vp]
     lib.ltr_head_train_workspace_bytes.argtypes = [vp, i32, i32]
@@ -172,7 +183,7 @@ def _load() -> C.CDLL:
         if name not in ("ltr_last_error", "ltr_workspace_bytes", "ltr_abi_version", "ltr_train_workspace_bytes",
                         "ltr_train_attention_workspace_bytes", "ltr_neuralndcg_workspace_bytes",
                         "ltr_order_agreement_workspace_bytes", "ltr_head_workspace_bytes",
-                        "ltr_head_train_workspace_bytes"):
+                        "ltr_head_train_workspace_bytes", "ltr_head_encoder_workspace_bytes"):
             fn.restype = C.c_int
     if lib.ltr_abi_version() != ABI_VERSION:
         raise LtrError(f"{LIB_PATH} has ABI version {lib.ltr_abi_version()}, this binding needs {ABI_VERSION}: rebuild")

@@ -32,7 +32,9 @@ constexpr int HB_PLANE = HB_BM * HB_LD;             // halves per plane (X hi, X
 constexpr int HB_CLD = HB_BN + 1;                   // floats per row of the output layer's score tile
 static_assert(3 * HB_PLANE * 2 >= HB_BM * HB_CLD * 4, "the score tile reuses the operand planes");
 
-// stats[r] = (mean, rstd, 1) with norm, (0, 1, split_scale(max|x|)) without; one wave per row, lanes own groups of four
+// stats[r] = (mean, rstd, 1) with norm, (0, 1, split_scale(max|x|)) without; one wave per row, lanes own groups of four.
+// norm == HEAD_NORM_ALLRANK: the encoder's LayerNorm (train/allrank/models/transformer.py:75-97) - unbiased std, eps added
+// to std - as (mean, 1 / (std + eps)) in the same two slots, so the dense kernel's loader folds it in like nn.LayerNorm
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(HB_THREADS) head_rows_kernel(const T* __restrict__ x, const T* __restrict__ res,
                                                                const int32_t* __restrict__ row_index, int N, int K,
@@ -54,7 +56,8 @@ __global__ void __launch_bounds__(HB_THREADS) head_rows_kernel(const T* __restri
 #pragma unroll
       for (int i = 0; i < 4; ++i) { const float d = c + i < K ? o[i] - mean : 0.f; sq += d * d; }
     }
-    rstd = rsqrtf(wave_sum(sq) / (float)K + LN_EPS);
+    rstd = norm == HEAD_NORM_ALLRANK ? 1.f / (sqrtf(wave_sum(sq) / (float)(K - 1)) + ALLRANK_LN_EPS)
+                                     : rsqrtf(wave_sum(sq) / (float)K + LN_EPS);
   } else {
     float amax = 0.f;
     for (int c = lane * 4; c < K; c += 256) {
@@ -65,20 +68,6 @@ __global__ void __launch_bounds__(HB_THREADS) head_rows_kernel(const T* __restri
   }
   if (lane == 0) { stats[3 * (size_t)r] = mean; stats[3 * (size_t)r + 1] = rstd; stats[3 * (size_t)r + 2] = scale; }
 }
-
-struct DenseArgs {
-  const void* x;             // [rows, K] of T
-  const void* res;           // same shape and dtype, or nullptr
-  const int32_t* row_index;  // [N] or nullptr
-  float* stats;              // [N][3] of head_rows_kernel
-  const float* ln_w;         // [K]; non-null: the tile is LayerNorm'd on load
-  const float* ln_b;
-  const __half* w;           // [O, K] row-major (nn.Linear layout)
-  const float* bias;         // [O]
-  float* out;                // f32 [N, O]; unused when scores is set
-  float* scores;             // non-null: output layer with O <= HB_BN, scores[r] = sum_j act(y[r][j]) in index order
-  int N, K, O, act;
-};
 
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(HB_THREADS) head_dense_kernel(DenseArgs a) {
@@ -202,7 +191,10 @@ __global__ void __launch_bounds__(HB_THREADS) head_dense_kernel(DenseArgs a) {
         const int tr = wr * 32 + i * 16 + 4 * (lane >> 4) + e, gr = m0 + tr;
         const float v = apply_act(acc[i][j][e] * s_inv[tr] + bj, a.act);
         if (a.scores) s_c[tr * HB_CLD + tc] = gc < a.O ? v : 0.f;
-        else if (gr < a.N && gc < a.O) a.out[(size_t)gr * a.O + gc] = v;
+        else if (gr < a.N && gc < a.O) {
+          const size_t o = (size_t)gr * a.O + gc;
+          a.out[o] = a.resid ? a.resid[o] + v : v;      // the element is read and written by this thread alone: resid may be out
+        }
       }
   }
   if (a.scores) {     // OutputLayer.score: the sum over d_output runs in index order, as the row kernel's
@@ -225,7 +217,6 @@ __global__ void __launch_bounds__(HB_THREADS) head_sum_kernel(const float* __res
   scores[r] = s;
 }
 
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // widest activation that goes through the workspace: every FC layer's, and the output layer's when it is not reduced in place
@@ -238,7 +229,7 @@ int ws_width(const HeadModel* m) {
 
 template <typename T, bool VEC> void launch_layer_v(const DenseArgs& a, hipStream_t s) {
   head_rows_kernel<T, VEC><<<(a.N + 3) / 4, HB_THREADS, 0, s>>>((const T*)a.x, (const T*)a.res, a.row_index, a.N, a.K,
-                                                               a.ln_w != nullptr, a.stats);
+                                                               a.ln_w != nullptr ? a.norm_kind : 0, a.stats);
   head_dense_kernel<T, VEC><<<dim3((a.N + HB_BM - 1) / HB_BM, (a.O + HB_BN - 1) / HB_BN), HB_THREADS, 0, s>>>(a);
 }
 
@@ -248,6 +239,47 @@ template <typename T> void launch_layer(const DenseArgs& a, hipStream_t s) {
 }
 
 }  // namespace
+
+int head_ws_width(const HeadModel* m) { return ws_width(m); }
+
+void launch_head_dense(const DenseArgs& a, int x_dtype, hipStream_t s) {
+  if (x_dtype == LTR_HID_F32) launch_layer<float>(a, s);
+  else if (x_dtype == LTR_HID_F16) launch_layer<__half>(a, s);
+  else launch_layer<bf16_t>(a, s);
+}
+
+int launch_head_layers(const HeadModel* m, int li0, int li1, const void* x, const void* res, int x_dtype,
+                       const int32_t* row_index, const float* ln_w, const float* ln_b, int norm_kind, int N, float* stats,
+                       float* const buf[2], float* scores_out, hipStream_t s, const float** cur_out) {
+  const float* cur = nullptr;
+  for (int li = li0; li < li1; ++li) {
+    const bool first = li == li0, last = li == m->L.n - 1;
+    DenseArgs a;
+    a.x = first ? x : (const void*)cur;
+    a.res = first ? res : nullptr;
+    a.row_index = first ? row_index : nullptr;
+    a.stats = stats;
+    a.ln_w = first ? ln_w : nullptr;
+    a.ln_b = first ? ln_b : nullptr;
+    a.norm_kind = norm_kind;
+    a.w = (const __half*)m->L.w[li];
+    a.bias = m->L.b[li];
+    a.out = buf[li & 1];
+    a.scores = last && m->L.out[li] <= HB_BN ? scores_out : nullptr;
+    a.N = N; a.K = m->L.in[li]; a.O = m->L.out[li];
+    a.act = last ? m->d.output_activation : m->d.activation;
+    launch_head_dense(a, first ? x_dtype : LTR_HID_F32, s);
+    LTR_LAUNCH_CHECK();
+    cur = a.out;
+  }
+  if (li1 == m->L.n && m->L.out[li1 - 1] > HB_BN) {
+    head_sum_kernel<<<(N + HB_THREADS - 1) / HB_THREADS, HB_THREADS, 0, s>>>(cur, N, m->L.out[li1 - 1], scores_out);
+    LTR_LAUNCH_CHECK();
+  }
+  if (cur_out) *cur_out = cur;
+  return LTR_OK;
+}
+
 }  // namespace ltr
 
 using namespace ltr;
@@ -287,33 +319,8 @@ int ltr_head_score_batched(ltr_head_handle h, const void* hidden, const void* re
   float* stats = (float*)ws;
   float* buf[2] = {(float*)(ws + align256((size_t)N * 3 * sizeof(float))),
                    (float*)(ws + align256((size_t)N * 3 * sizeof(float)) + act_bytes)};
-  const float* cur = nullptr;
-  for (int li = 0; li < m->L.n; ++li) {
-    const bool last = li == m->L.n - 1;
-    DenseArgs a;
-    a.x = li == 0 ? hidden : (const void*)cur;
-    a.res = li == 0 ? residual : nullptr;
-    a.row_index = li == 0 ? row_index : nullptr;
-    a.stats = stats;
-    a.ln_w = li == 0 ? m->ln_w : nullptr;
-    a.ln_b = li == 0 ? m->ln_b : nullptr;
-    a.w = (const __half*)m->L.w[li];
-    a.bias = m->L.b[li];
-    a.out = buf[li & 1];
-    a.scores = last && m->L.out[li] <= HB_BN ? scores_out : nullptr;
-    a.N = N; a.K = m->L.in[li]; a.O = m->L.out[li];
-    a.act = last ? m->d.output_activation : m->d.activation;
-    if (li > 0 || hidden_dtype == LTR_HID_F32) launch_layer<float>(a, s);
-    else if (hidden_dtype == LTR_HID_F16) launch_layer<__half>(a, s);
-    else launch_layer<bf16_t>(a, s);
-    LTR_LAUNCH_CHECK();
-    cur = a.out;
-  }
-  if (m->L.out[m->L.n - 1] > HB_BN) {
-    head_sum_kernel<<<(N + HB_THREADS - 1) / HB_THREADS, HB_THREADS, 0, s>>>(cur, N, m->L.out[m->L.n - 1], scores_out);
-    LTR_LAUNCH_CHECK();
-  }
-  return LTR_OK;
+  return launch_head_layers(m, 0, m->L.n, hidden, residual, hidden_dtype, row_index, m->ln_w, m->ln_b, HEAD_NORM_TORCH, N,
+                            stats, buf, scores_out, s, nullptr);
 }
 
 }  // extern "C"

@@ -323,6 +323,37 @@ struct HeadModel {
   int maxw;
 };
 
+// ---- batched MFMA path of the head (ltr_head_mfma.hip), shared with the slate encoder (ltr_head_encoder.hip) ----
+constexpr float ALLRANK_LN_EPS = 1e-6f;   // allRank's LayerNorm: added to the unbiased std (transformer.py:79,97)
+enum { HEAD_NORM_TORCH = 1, HEAD_NORM_ALLRANK = 2 };
+
+struct DenseArgs {
+  const void* x;             // [rows, K] of T
+  const void* res;           // same shape and dtype, or nullptr
+  const int32_t* row_index;  // [N] or nullptr
+  float* stats;              // [N][3] of head_rows_kernel
+  const float* ln_w;         // [K]; non-null: the tile is LayerNorm'd on load
+  const float* ln_b;
+  const __half* w;           // [O, K] row-major (nn.Linear layout)
+  const float* bias;         // [O]
+  const float* resid = nullptr;   // f32 [N, O] added after the activation, or nullptr (may be `out`; not with scores)
+  int norm_kind = 1;         // HEAD_NORM_* of the statistics when ln_w is set
+  float* out;                // f32 [N, O]; unused when scores is set
+  float* scores;             // non-null: output layer with O <= HB_BN, scores[r] = sum_j act(y[r][j]) in index order
+  int N, K, O, act;
+};
+
+inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+// widest activation the head's own layers put through the workspace
+int head_ws_width(const HeadModel* m);
+// head_rows_kernel + head_dense_kernel for one dense layer; x_dtype = LTR_HID_* of a.x / a.res
+void launch_head_dense(const DenseArgs& a, int x_dtype, hipStream_t s);
+// dense layers [li0, li1) of the head: layer li0 reads x (x_dtype, with res / row_index / the norm given), layer li writes
+// buf[li & 1]; the output layer (li1 == L.n) writes scores_out.  *cur_out: the last activation written
+int launch_head_layers(const HeadModel* m, int li0, int li1, const void* x, const void* res, int x_dtype,
+                       const int32_t* row_index, const float* ln_w, const float* ln_b, int norm_kind, int N, float* stats,
+                       float* const buf[2], float* scores_out, hipStream_t s, const float** cur_out);
+
 // largest i in [0, n) with cu[i] <= t   (cu ascending, cu[0] <= t < cu[n])
 __device__ __forceinline__ int find_request(const int32_t* __restrict__ cu, int n, int t) {
   int lo = 0, hi = n;  // answer in [lo, hi)

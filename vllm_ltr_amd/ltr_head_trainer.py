@@ -39,7 +39,10 @@ class HipLTRHeadTrainer:
                  state: Optional[Dict[str, np.ndarray]] = None, lr: float = 1e-3, weight_decay: float = 0.0,
                  loss: str = "listMLE", clip_norm: Optional[float] = None, device: str = "cuda:0",
                  betas=(0.9, 0.999), eps: float = 1e-8, listmle_eps: float = DEFAULT_EPS,
-                 pad_value: float = PADDED_Y_VALUE):
+                 pad_value: float = PADDED_Y_VALUE, transformer: Optional[dict] = None):
+        if transformer:
+            raise NotImplementedError("HipLTRHeadTrainer: training the slate encoder (ModelConfig.transformer) is not built; "
+                                      "HipLTRHead scores a checkpoint that allRank trained with one")
         if fc_model and fc_model.get("dropout"):
             raise NotImplementedError("HipLTRHeadTrainer: FCModel's dropout is not built (the device training step covers "
                                       "the dense layers, the input LayerNorm and the six activations)")
