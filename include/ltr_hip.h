@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LTR_ABI_VERSION 11
+#define LTR_ABI_VERSION 12
 
 enum {
   LTR_OK = 0,
@@ -416,6 +416,45 @@ int ltr_neuralndcg(const float* y_pred, const float* y_true, int32_t B, int32_t 
                    float pad_value, float* loss_out, float* row_ndcg_out, float* grad_out, void* workspace,
                    size_t ws_bytes, void* stream);
 
+/* The LambdaLoss family (ABI 12): train/allrank/models/losses/lambdaLoss.py:23-130 and its gradient w.r.t. the
+ * predictions, computed pair by pair in registers - nothing of size [S, S] is written to memory.  y_pred, y_true f32 [B, S],
+ * 1 <= S <= 4096.  Per slate:
+ *   valid items  y_true != pad_value; the others take no part and get gradient 0
+ *   rank(i)      0-based position of item i under descending score among the valid items; equal scores: the lower index first
+ *                (torch.sort leaves this open)
+ *   cut          kk = S when k <= 0 or k > S, else k (the reference's None)
+ *   D[r] = log2(2 + r) in f32;  maxDCG = max(sum over the kk largest labels of (2^label - 1) / D[position], eps);
+ *   G_i = (2^label_i - 1) / maxDCG   (labels below 0 count as 0 in gains and weights, lambdaLoss.py:64-65)
+ *   pair (i, j)  selected when both are valid, rank(i) < kk, rank(j) < kk and label_i > label_j; ndcgLoss1_scheme has no label
+ *                condition and selects the diagonal i == j too (it adds to the loss and gives no gradient)
+ *   weight w_ij  by `scheme`, with d = |rank_i - rank_j|, l2 = |1/D[d-1] - 1/D[d]| |G_i - G_j| (0 for d = 0) and
+ *                lr = |1/D[rank_i] - 1/D[rank_j]| |G_i - G_j|:
+ *                  0 none, 1 rankNet_scheme: 1           2 ndcgLoss1_scheme: G_i / D[rank_i]      3 ndcgLoss2_scheme: l2
+ *                  4 lambdaRank_scheme: lr               5 ndcgLoss2PP_scheme: mu l2 + lr
+ *                  6 rankNetWeightedByGTDiff_scheme: |label_i - label_j|      7 ...GTDiffPowed_scheme: |label_i^2 - label_j^2|
+ *   term         x = clamp(s_i - s_j, +-1e8), p = max(sigmoid(sigma x), eps), q = max(p^w, eps), log2 q (log_base 0) or ln q (1)
+ *   loss         -(sum of the terms over the selected pairs of the WHOLE batch), divided by their number under reduction 1
+ *   gradient     the weights are constants (ranks, labels and gains are not differentiated): dterm / ds_i = w sigma (1 - p) / c,
+ *                c = ln 2 (binary) or 1 (natural), the negative at j, 0 where either clamp is active
+ *   no selected pair: loss 0 and a zero gradient (the reference's mean of an empty selection is NaN).
+ * loss_out f32 [1]; grad_out f32 [B, S] or NULL; workspace: the bytes the sizing call names (0 for an unsupported shape), device.
+ * A bad config value, a NULL pointer, S > 4096 or B > 65535: LTR_E_INVAL; a short workspace: LTR_E_NOMEM; nothing is launched and
+ * the checks never touch the device.  B * S == 0: LTR_OK, nothing is written.  Three launches on `stream`; no atomics, no memset,
+ * no host sync: two calls give identical bits, and the call can be captured into a graph. */
+typedef struct ltr_lambdaloss_config {
+  int32_t scheme;       /* 0 .. 7, the table above */
+  int32_t k;            /* rank the loss is truncated at; <= 0 or > S: the slate length */
+  float sigma;          /* <= 0: 1 */
+  float mu;             /* ndcgLoss2PP_scheme only (the reference's default is 10) */
+  int32_t reduction;    /* 0 sum, 1 mean */
+  int32_t log_base;     /* 0 binary, 1 natural */
+  float eps;            /* allrank DEFAULT_EPS 1e-10; must lie in (0, 1) */
+  float pad_value;      /* allrank PADDED_Y_VALUE -1 */
+} ltr_lambdaloss_config;
+size_t ltr_lambdaloss_workspace_bytes(int32_t B, int32_t S);
+int ltr_lambdaloss(const float* y_pred, const float* y_true, int32_t B, int32_t S, const ltr_lambdaloss_config* cfg,
+                   float* loss_out, float* grad_out, void* workspace, size_t ws_bytes, void* stream);
+
 /* Order agreement of two score vectors (ABI 8): the pair counts behind the reference's training metric, Kendall's tau
  * (train/trainer.py:195: scipy.stats.kendalltau(labels, predictions) after every epoch), and the discordant-pair gaps by which
  * two queue orders are compared (the orders benchmarks/benchmark_throughput_original.py:396-443 schedules by).  x, y f32 [n];
@@ -500,12 +539,15 @@ int ltr_train_read(ltr_train_handle h, int32_t index, int32_t what, float* dst, 
  * NOT built: dropout (FCModel's nn.Dropout, model.py:45-66 - a head with dropout is outside this interface), the gradient
  * w.r.t. `hidden`, and stream capture of a step (Adam's bias corrections are host-side arguments of a launch). */
 enum { LTR_HEAD_LOSS_GIVEN = 4 };   /* y_true holds dLoss/dscore [B, S] (a loss computed elsewhere); loss_out is not touched */
+enum { LTR_HEAD_LOSS_LAMBDA = 5 };  /* the LambdaLoss family on the [B, S] scores, configured by ltr_head_train_config.lambda (ABI 12) */
 typedef struct ltr_head_train_config {
   float lr, beta1, beta2, eps, weight_decay;   /* torch.optim.Adam (train_utils.py:34-45 steps the optimizer it is handed) */
-  int32_t loss;          /* LTR_LOSS_LISTMLE | LTR_LOSS_MSE | LTR_LOSS_NEURALNDCG | LTR_HEAD_LOSS_GIVEN; LTR_LOSS_CROSSENTROPY: LTR_E_INVAL */
+  int32_t loss;          /* LTR_LOSS_LISTMLE | LTR_LOSS_MSE | LTR_LOSS_NEURALNDCG | LTR_HEAD_LOSS_GIVEN | LTR_HEAD_LOSS_LAMBDA;
+                            LTR_LOSS_CROSSENTROPY: LTR_E_INVAL */
   float listmle_eps;     /* allrank DEFAULT_EPS 1e-10 */
   float pad_value;       /* allrank PADDED_Y_VALUE -1 */
   float clip_norm;       /* clip_grad_norm_ (train_utils.py:40-41); <= 0: off */
+  ltr_lambdaloss_config lambda;   /* ABI 12, appended: read under LTR_HEAD_LOSS_LAMBDA only (all zero is fine for every other loss) */
 } ltr_head_train_config;
 typedef struct ltr_head_trainer* ltr_head_train_handle;
 /* replaces predictor_model's construction + the optimizer's state (predictor.py:126-145): COPIES the f32 weights - pointer
@@ -525,7 +567,8 @@ size_t ltr_head_train_workspace_bytes(ltr_head_train_handle h, int32_t B, int32_
  *   apply_update 1: the step; 0: gradients only (moments and step count stay)
  *   loss_out f32 [1]; scores_out f32 [B, S] or NULL: the scores BEFORE the update; grad_norm_out f32 [1] or NULL: the
  *   global L2 norm of all gradients before clipping.  All device memory.
- * Argument errors (NULL pointer, bad dtype, neuralNDCG outside 2 <= S <= 1024, listMLE without shuffle or S > 4096):
+ * Argument errors (NULL pointer, bad dtype, neuralNDCG outside 2 <= S <= 1024, listMLE without shuffle, listMLE or LambdaLoss
+ * with S > 4096):
  * LTR_E_INVAL; short workspace: LTR_E_NOMEM; nothing is launched.  B * S == 0: LTR_OK. */
 int ltr_head_train_step(ltr_head_train_handle h, const void* hidden, const void* residual, int32_t hidden_dtype,
                         const int32_t* row_index, int32_t B, int32_t S, const float* y_true, const int32_t* shuffle,

@@ -32,8 +32,8 @@ SYMBOLS = ("ltr_abi_version", "ltr_last_error", "ltr_create", "ltr_destroy", "lt
            "ltr_train_attention_workspace_bytes", "ltr_head_train_create", "ltr_head_train_destroy",
            "ltr_head_train_workspace_bytes", "ltr_head_train_step", "ltr_head_train_read",
            "ltr_head_encoder_create", "ltr_head_encoder_destroy", "ltr_head_encoder_workspace_bytes",
-           "ltr_head_encoder_score")
-ABI_VERSION = 11
+           "ltr_head_encoder_score", "ltr_lambdaloss", "ltr_lambdaloss_workspace_bytes")
+ABI_VERSION = 12
 
 
 LTR_E_INVAL, LTR_E_RANGE, LTR_E_NOMEM = -22, -34, -12
@@ -75,14 +75,38 @@ class TrainConfig(C.Structure):
                 ("dropout", C.c_float), ("precision", C.c_int32), ("seed", C.c_uint64)]
 
 
+class LambdaLossConfig(C.Structure):
+    """``ltr_lambdaloss_config``; all zero is valid wherever the loss is not LambdaLoss."""
+    _fields_ = [("scheme", C.c_int32), ("k", C.c_int32), ("sigma", C.c_float), ("mu", C.c_float),
+                ("reduction", C.c_int32), ("log_base", C.c_int32), ("eps", C.c_float), ("pad_value", C.c_float)]
+
+
+# allRank's names (losses/lambdaLoss.py:100-130) -> ltr_lambdaloss_config.scheme / .reduction / .log_base
+LAMBDA_SCHEMES = {None: 0, "rankNet_scheme": 1, "ndcgLoss1_scheme": 2, "ndcgLoss2_scheme": 3, "lambdaRank_scheme": 4,
+                  "ndcgLoss2PP_scheme": 5, "rankNetWeightedByGTDiff_scheme": 6, "rankNetWeightedByGTDiffPowed_scheme": 7}
+LAMBDA_REDUCTIONS = {"sum": 0, "mean": 1}
+LAMBDA_LOGS = {"binary": 0, "natural": 1}
+
+
+def lambdaloss_config(weighing_scheme=None, k=None, sigma=1.0, mu=10.0, reduction="sum", reduction_log="binary",
+                      eps=1e-10, padded_value_indicator=-1) -> LambdaLossConfig:
+    """lambdaLoss's keywords (lambdaLoss.py:23-24) as the C struct; an unknown name raises ValueError naming it."""
+    for what, name, table in (("weighing_scheme", weighing_scheme, LAMBDA_SCHEMES), ("reduction", reduction, LAMBDA_REDUCTIONS),
+                              ("reduction_log", reduction_log, LAMBDA_LOGS)):
+        if name not in table:
+            raise ValueError(f"lambdaLoss: {what} {name!r} (one of {sorted(table, key=str)})")
+    return LambdaLossConfig(LAMBDA_SCHEMES[weighing_scheme], int(k or 0), float(sigma), float(mu), LAMBDA_REDUCTIONS[reduction],
+                            LAMBDA_LOGS[reduction_log], float(eps), float(padded_value_indicator))
+
+
 class HeadTrainConfig(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float), ("loss", C.c_int32), ("listmle_eps", C.c_float), ("pad_value", C.c_float),
-                ("clip_norm", C.c_float)]
+                ("clip_norm", C.c_float), ("lambda_", LambdaLossConfig)]     # (`lambda` in C; read under LTR_HEAD_LOSS_LAMBDA only)
 
 
-LTR_HEAD_LOSS_GIVEN = 4
-HEAD_LOSSES = {"listMLE": 0, "mse": 1, "neuralNDCG": 3, "given": LTR_HEAD_LOSS_GIVEN}
+LTR_HEAD_LOSS_GIVEN, LTR_HEAD_LOSS_LAMBDA = 4, 5
+HEAD_LOSSES = {"listMLE": 0, "mse": 1, "neuralNDCG": 3, "given": LTR_HEAD_LOSS_GIVEN, "lambdaLoss": LTR_HEAD_LOSS_LAMBDA}
 LOSSES = {"listMLE": 0, "mse": 1, "crossentropy": 2, "neuralNDCG": 3}
 TRAIN_PRECISIONS = {None: 0, "split": 1, "f32": 2}
 
@@ -149,6 +173,9 @@ def _load() -> C.CDLL:
     lib.ltr_neuralndcg.argtypes = [vp, vp, i32, i32, C.c_float, i32, C.c_float, vp, vp, vp, vp, sz, vp]
     lib.ltr_neuralndcg_workspace_bytes.argtypes = [i32, i32]
     lib.ltr_neuralndcg_workspace_bytes.restype = sz
+    lib.ltr_lambdaloss_workspace_bytes.argtypes = [i32, i32]
+    lib.ltr_lambdaloss_workspace_bytes.restype = sz
+    lib.ltr_lambdaloss.argtypes = [vp, vp, i32, i32, C.POINTER(LambdaLossConfig), vp, vp, vp, sz, vp]
     lib.ltr_order_agreement_workspace_bytes.argtypes = [i64]
     lib.ltr_order_agreement_workspace_bytes.restype = sz
     lib.ltr_order_agreement.argtypes = [vp, vp, i32, vp, vp, sz, vp]
@@ -183,7 +210,8 @@ def _load() -> C.CDLL:
         if name not in ("ltr_last_error", "ltr_workspace_bytes", "ltr_abi_version", "ltr_train_workspace_bytes",
                         "ltr_train_attention_workspace_bytes", "ltr_neuralndcg_workspace_bytes",
                         "ltr_order_agreement_workspace_bytes", "ltr_head_workspace_bytes",
-                        "ltr_head_train_workspace_bytes", "ltr_head_encoder_workspace_bytes"):
+                        "ltr_head_train_workspace_bytes", "ltr_head_encoder_workspace_bytes",
+                        "ltr_lambdaloss_workspace_bytes"):
             fn.restype = C.c_int
     if lib.ltr_abi_version() != ABI_VERSION:
         raise LtrError(f"{LIB_PATH} has ABI version {lib.ltr_abi_version()}, this binding needs {ABI_VERSION}: rebuild")

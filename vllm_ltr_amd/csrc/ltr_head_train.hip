@@ -647,7 +647,8 @@ HtWs carve(const ltr_head_trainer* t, int B, int S, void* base) {
   w.dw_part = take(dwp * 4);
   w.sq_part = take(HT_SQ_NB * 4);
   w.slots = take(64);
-  w.ndcg_bytes = t->cfg.loss == LTR_LOSS_NEURALNDCG ? ltr_neuralndcg_workspace_bytes(B, S) : 0;
+  w.ndcg_bytes = t->cfg.loss == LTR_LOSS_NEURALNDCG ? ltr_neuralndcg_workspace_bytes(B, S)
+                 : t->cfg.loss == LTR_HEAD_LOSS_LAMBDA ? ltr_lambdaloss_workspace_bytes(B, S) : 0;
   w.ndcg = take(w.ndcg_bytes);
   w.bytes = o;
   return w;
@@ -722,6 +723,9 @@ int run_step(ltr_head_trainer* t, XSrc x0, int B, int S, const float* y_true, co
       break;
     case LTR_LOSS_NEURALNDCG:
       rc = ltr_neuralndcg(w.scores, y_true, B, S, 1.f, 0, t->cfg.pad_value, loss_out, w.row_loss, w.dscore, w.ndcg, w.ndcg_bytes, s);
+      break;
+    case LTR_HEAD_LOSS_LAMBDA:
+      rc = ltr_lambdaloss(w.scores, y_true, B, S, &t->cfg.lambda, loss_out, w.dscore, w.ndcg, w.ndcg_bytes, s);
       break;
     case LTR_LOSS_MSE:
       ht_mse_kernel<<<1, HT_THREADS, 0, s>>>(w.scores, y_true, M, loss_out, w.dscore);
@@ -823,8 +827,13 @@ int ltr_head_train_create(const ltr_head_desc* d, const void* const* weights, in
   if (d->activation < LTR_ACT_NONE || d->activation > LTR_ACT_SILU || d->output_activation < LTR_ACT_NONE || d->output_activation > LTR_ACT_SILU) {
     set_error("ltr_head_train_create: unknown activation"); return LTR_E_INVAL;
   }
-  if (cfg->loss != LTR_LOSS_LISTMLE && cfg->loss != LTR_LOSS_MSE && cfg->loss != LTR_LOSS_NEURALNDCG && cfg->loss != LTR_HEAD_LOSS_GIVEN) {
-    set_error("ltr_head_train_create: loss %d is not listMLE, MSE, neuralNDCG or LTR_HEAD_LOSS_GIVEN", cfg->loss); return LTR_E_INVAL;
+  if (cfg->loss != LTR_LOSS_LISTMLE && cfg->loss != LTR_LOSS_MSE && cfg->loss != LTR_LOSS_NEURALNDCG && cfg->loss != LTR_HEAD_LOSS_GIVEN &&
+      cfg->loss != LTR_HEAD_LOSS_LAMBDA) {
+    set_error("ltr_head_train_create: loss %d is not listMLE, MSE, neuralNDCG, LTR_HEAD_LOSS_GIVEN or LTR_HEAD_LOSS_LAMBDA", cfg->loss); return LTR_E_INVAL;
+  }
+  if (cfg->loss == LTR_HEAD_LOSS_LAMBDA) {         // the checks of ltr_lambdaloss, made once (an empty slate touches nothing)
+    const int rc = ltr_lambdaloss(nullptr, nullptr, 0, 0, &cfg->lambda, nullptr, nullptr, nullptr, 0, nullptr);
+    if (rc) return rc;
   }
   const int want = 2 + 2 * (d->n_fc + 1);
   if (n_weights != want) { set_error("ltr_head_train_create: %d weight pointers, expected %d", n_weights, want); return LTR_E_INVAL; }
@@ -903,6 +912,9 @@ int ltr_head_train_step(ltr_head_train_handle h, const void* hidden, const void*
   const int loss = h->cfg.loss;
   if (!hidden || !y_true || !workspace || (loss != LTR_HEAD_LOSS_GIVEN && !loss_out)) { set_error("ltr_head_train_step: NULL argument"); return LTR_E_INVAL; }
   if (loss == LTR_LOSS_LISTMLE && (!shuffle || S > 4096)) { set_error("ltr_head_train_step: listMLE needs the shuffle permutation and S <= 4096"); return LTR_E_INVAL; }
+  if (loss == LTR_HEAD_LOSS_LAMBDA && (S > 4096 || ltr_lambdaloss_workspace_bytes(B, S) == 0)) {
+    set_error("ltr_head_train_step: LambdaLoss takes slates of at most 4096 items and 65535 slates ([%d, %d])", B, S); return LTR_E_INVAL;
+  }
   if (loss == LTR_LOSS_NEURALNDCG && (S < 2 || S > 1024 || ltr_neuralndcg_workspace_bytes(B, S) == 0)) {
     set_error("ltr_head_train_step: neuralNDCG takes slates of 2..1024 items (S = %d)", S); return LTR_E_INVAL;
   }

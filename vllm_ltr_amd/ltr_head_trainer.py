@@ -39,7 +39,9 @@ class HipLTRHeadTrainer:
                  state: Optional[Dict[str, np.ndarray]] = None, lr: float = 1e-3, weight_decay: float = 0.0,
                  loss: str = "listMLE", clip_norm: Optional[float] = None, device: str = "cuda:0",
                  betas=(0.9, 0.999), eps: float = 1e-8, listmle_eps: float = DEFAULT_EPS,
-                 pad_value: float = PADDED_Y_VALUE, transformer: Optional[dict] = None):
+                 pad_value: float = PADDED_Y_VALUE, transformer: Optional[dict] = None, loss_args: Optional[dict] = None):
+        """``loss_args``: allRank's ``loss.args`` of ``"lambdaLoss"`` (lambdaLoss.py:23-24: weighing_scheme, k, sigma, mu, reduction,
+        reduction_log, eps, padded_value_indicator); eps and the padding value default to ``listmle_eps`` and ``pad_value``."""
         if transformer:
             raise NotImplementedError("HipLTRHeadTrainer: training the slate encoder (ModelConfig.transformer) is not built; "
                                       "HipLTRHead scores a checkpoint that allRank trained with one")
@@ -48,6 +50,13 @@ class HipLTRHeadTrainer:
                                       "the dense layers, the input LayerNorm and the six activations)")
         if loss not in _lib.HEAD_LOSSES:
             raise ValueError(f"HipLTRHeadTrainer: loss {loss!r} (one of {sorted(_lib.HEAD_LOSSES)})")
+        if loss_args and loss != "lambdaLoss":
+            raise ValueError(f"HipLTRHeadTrainer: loss_args configure lambdaLoss, not {loss!r}")
+        try:
+            lam = (_lib.lambdaloss_config(**{"eps": listmle_eps, "padded_value_indicator": pad_value, **(loss_args or {})})
+                   if loss == "lambdaLoss" else _lib.LambdaLossConfig())
+        except TypeError as e:
+            raise ValueError(f"HipLTRHeadTrainer: loss_args {sorted(loss_args)}: {e}") from None
         if not torch.cuda.is_available():
             raise _lib.LtrError("HipLTRHeadTrainer needs a ROCm GPU (no CPU fallback on the product path)")
         self.lib = _lib.load()
@@ -74,7 +83,7 @@ class HipLTRHeadTrainer:
         desc.output_activation = _lib.ACTIVATIONS[post_model.get("output_activation")]
         desc.weight_dtype = _lib.LTR_W_F32
         cfg = _lib.HeadTrainConfig(lr, betas[0], betas[1], eps, weight_decay, _lib.HEAD_LOSSES[loss], listmle_eps,
-                                   pad_value, float(clip_norm) if clip_norm else 0.0)
+                                   pad_value, float(clip_norm) if clip_norm else 0.0, lam)
         ptrs = (C.c_void_p * len(t))(*[(x.data_ptr() if x is not None else None) for x in t])
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
