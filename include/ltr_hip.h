@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LTR_ABI_VERSION 12
+#define LTR_ABI_VERSION 13
 
 enum {
   LTR_OK = 0,
@@ -556,6 +556,17 @@ typedef struct ltr_head_trainer* ltr_head_train_handle;
  * which it synchronises. */
 int ltr_head_train_create(const ltr_head_desc* desc, const void* const* weights_f32, int32_t n_weights,
                           const ltr_head_train_config* cfg, void* stream, ltr_head_train_handle* out);
+/* The same trainer with allRank's slate encoder between the FC stack and the output layer (ABI 13; DESIGN.md 4.4 "training
+ * the encoder"): FCModel -> Encoder -> OutputLayer, train/allrank/models/transformer.py:44-263 wired by models/model.py:147-161.
+ * A step's [B, S] batch is B slates of S items; attention stays inside a slate and masks item j as a KEY when
+ * y_true[b, j] == cfg.pad_value (transformer.py:166-167; no labels and so no mask under LTR_HEAD_LOSS_GIVEN).  A query row
+ * whose slate has no valid key gets attention output 0 and passes no gradient (the reference gives NaN there); a padded row
+ * still yields a score.  The returned handle is served by ltr_head_train_step / _workspace_bytes / _read / _destroy.
+ * Shape limits and the encoder's 12 n_blocks + 2 weight pointers as in ltr_head_encoder_create, every tensor f32, after the
+ * head's pointers; ltr_head_train_read's index runs over that order.  NOT built: dropout, positional encoding, B > 65535. */
+int ltr_head_train_create_encoder(const ltr_head_desc* desc, const ltr_head_encoder_desc* enc,
+                                  const void* const* weights_f32, int32_t n_weights,
+                                  const ltr_head_train_config* cfg, void* stream, ltr_head_train_handle* out);
 int ltr_head_train_destroy(ltr_head_train_handle h);
 /* reference: no counterpart (torch allocates activations and gradients); bytes for a [B, S] slate, 0 for B * S <= 0 */
 size_t ltr_head_train_workspace_bytes(ltr_head_train_handle h, int32_t B, int32_t S);

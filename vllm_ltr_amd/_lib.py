@@ -29,11 +29,11 @@ SYMBOLS = ("ltr_abi_version", "ltr_last_error", "ltr_create", "ltr_destroy", "lt
            "ltr_neuralndcg", "ltr_neuralndcg_workspace_bytes", "ltr_order_agreement", "ltr_order_agreement_workspace_bytes",
            "ltr_status", "ltr_queue_step", "ltr_train_create", "ltr_train_destroy", "ltr_train_workspace_bytes",
            "ltr_train_step", "ltr_train_read", "ltr_attention", "ltr_train_attention",
-           "ltr_train_attention_workspace_bytes", "ltr_head_train_create", "ltr_head_train_destroy",
+           "ltr_train_attention_workspace_bytes", "ltr_head_train_create", "ltr_head_train_create_encoder", "ltr_head_train_destroy",
            "ltr_head_train_workspace_bytes", "ltr_head_train_step", "ltr_head_train_read",
            "ltr_head_encoder_create", "ltr_head_encoder_destroy", "ltr_head_encoder_workspace_bytes",
            "ltr_head_encoder_score", "ltr_lambdaloss", "ltr_lambdaloss_workspace_bytes")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 LTR_E_INVAL, LTR_E_RANGE, LTR_E_NOMEM = -22, -34, -12
@@ -191,6 +191,8 @@ def _load() -> C.CDLL:
     lib.ltr_head_encoder_workspace_bytes.restype = sz
     lib.ltr_head_encoder_score.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, sz, vp]
     lib.ltr_head_train_create.argtypes = [C.POINTER(HeadDesc), C.POINTER(vp), i32, C.POINTER(HeadTrainConfig), vp, C.POINTER(vp)]
+    lib.ltr_head_train_create_encoder.argtypes = [C.POINTER(HeadDesc), C.POINTER(HeadEncoderDesc), C.POINTER(vp), i32,
+                                                  C.POINTER(HeadTrainConfig), vp, C.POINTER(vp)]
     lib.ltr_head_train_destroy.argtypes = [vp]
     lib.ltr_head_train_workspace_bytes.argtypes = [vp, i32, i32]
     lib.ltr_head_train_workspace_bytes.restype = sz

@@ -253,6 +253,20 @@ void launch_slate_attn(const float* qkv, const int32_t* cu, int N, int B, int ma
 size_t enc_act_width(const HeadEncoder* e) { return (size_t)max(head_ws_width(e->head), e->d_model); }
 
 }  // namespace
+
+int launch_enc_gather(const void* x, const void* res, int x_dtype, const int32_t* row_index, int N, int K, float* z,
+                      hipStream_t s) {
+  const unsigned blocks = (unsigned)(((size_t)N * ((K + 3) / 4) + SA_THREADS - 1) / SA_THREADS);
+  if (x_dtype == LTR_HID_F32)
+    enc_gather_kernel<float><<<blocks, SA_THREADS, 0, s>>>((const float*)x, (const float*)res, row_index, N, K, z);
+  else if (x_dtype == LTR_HID_F16)
+    enc_gather_kernel<__half><<<blocks, SA_THREADS, 0, s>>>((const __half*)x, (const __half*)res, row_index, N, K, z);
+  else
+    enc_gather_kernel<bf16_t><<<blocks, SA_THREADS, 0, s>>>((const bf16_t*)x, (const bf16_t*)res, row_index, N, K, z);
+  LTR_LAUNCH_CHECK();
+  return LTR_OK;
+}
+
 }  // namespace ltr
 
 using namespace ltr;
@@ -355,14 +369,8 @@ int ltr_head_encoder_score(ltr_head_encoder_handle enc, const void* hidden, cons
                                       HEAD_NORM_TORCH, N, stats, buf, nullptr, s, nullptr);
     if (rc != LTR_OK) return rc;
   } else {
-    const unsigned blocks = (unsigned)((n * ((dm + 3) / 4) + SA_THREADS - 1) / SA_THREADS);
-    if (hidden_dtype == LTR_HID_F32)
-      enc_gather_kernel<float><<<blocks, SA_THREADS, 0, s>>>((const float*)hidden, (const float*)residual, row_index, N, dm, z);
-    else if (hidden_dtype == LTR_HID_F16)
-      enc_gather_kernel<__half><<<blocks, SA_THREADS, 0, s>>>((const __half*)hidden, (const __half*)residual, row_index, N, dm, z);
-    else
-      enc_gather_kernel<bf16_t><<<blocks, SA_THREADS, 0, s>>>((const bf16_t*)hidden, (const bf16_t*)residual, row_index, N, dm, z);
-    LTR_LAUNCH_CHECK();
+    const int rc = launch_enc_gather(hidden, residual, hidden_dtype, row_index, N, dm, z, s);
+    if (rc != LTR_OK) return rc;
   }
   // 2. the blocks (EncoderLayer.forward, transformer.py:142-150)
   auto dense = [&](const float* x, const float* na, const float* nb, const __half* w, const float* bias, int K, int O,

@@ -29,6 +29,9 @@
 //   norm, clip          sum of squares per fixed chunk, then one thread adds the chunks in order (clip_grad_norm_)
 //   ht_adam_tile_kernel torch.optim.Adam on a 64 x 64 tile of a matrix + the refreshed hi | lo images of W and, through an
 //                       LDS transpose, of W^T; vectors use the element-wise form
+// With an encoder (ltr_head_train_create_encoder) the same kernels run its five dense layers per block - allRank's norm
+// rides on the tile loader's (x - mean) rstd g + b with rstd = 1 / (std + eps) - around the attention and norm kernels of
+// ltr_head_encoder_train.hip.
 // No atomics, no memset, no allocation in a step, no waiting between workgroups: every dependency is a launch boundary.
 // A step cannot be captured into a graph as it stands: Adam's bias corrections are host-side arguments.
 #include "ltr_internal.h"
@@ -36,6 +39,7 @@
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 namespace ltr {
@@ -55,6 +59,9 @@ constexpr int HT_CS_PART = 256;               // rows per part of a column sum
 constexpr int HT_SQ_NB = 256;                 // chunks of the sum of squares
 constexpr int HT_MAX_LAYERS = 9;              // 8 FC layers + the output layer
 constexpr int HT_MAX_ROWS = 1 << 22;
+constexpr int HT_ENC_BLOCKS = 16;             // most encoder blocks (ltr_head_encoder_create)
+constexpr int HT_ENC_PER_BLOCK = 12;          // tensors per encoder block: norm 0, QKV, W_o, norm 1, w_1, w_2 as (a, b) / (W, b)
+constexpr int HT_MAX_MATS = HT_MAX_LAYERS + 4 * HT_ENC_BLOCKS;
 
 // derivative of apply_act at pre-activation z (ReLU: 0 at 0, as torch)
 __device__ __forceinline__ float act_grad(float z, int act) {
@@ -438,6 +445,18 @@ __global__ void __launch_bounds__(HT_THREADS) ht_colparts_sum_kernel(const doubl
   out[c] = (float)s;
 }
 
+// out[c] = sum_j W[j][c] v[j] in f64, j in order.  The encoder's final norm feeds the output layer linearly, so its d b_2 =
+// sum_rows dZ_o W_o is W_o^T applied to the output bias's gradient, whose f64 column sum keeps what a shift-invariant loss
+// leaves of it; the column sum of the rounded rows dZ_o W_o would return their rounding instead (see ht_colsum_kernel)
+__global__ void __launch_bounds__(HT_THREADS) ht_matvec_t_kernel(const float* __restrict__ W, const float* __restrict__ v, int O, int K,
+                                                               float* __restrict__ out) {
+  const int c = blockIdx.x * HT_THREADS + threadIdx.x;
+  if (c >= K) return;
+  double s = 0.0;
+  for (int j = 0; j < O; ++j) s += (double)W[(size_t)j * K + c] * (double)v[j];
+  out[c] = (float)s;
+}
+
 // out[i] = sum_p partial[p][i] in part order (the weight-gradient parts of a narrow layer)
 __global__ void __launch_bounds__(HT_THREADS) ht_parts_sum_kernel(const float* __restrict__ partial, int parts, size_t n, float* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * HT_THREADS + threadIdx.x;
@@ -597,17 +616,23 @@ struct ltr_head_trainer {
   ltr_head_train_config cfg;
   int device = 0;
   int n = 0;                          // dense layers including the output layer
-  int in[HT_MAX_LAYERS], out[HT_MAX_LAYERS];
-  std::vector<size_t> off, cnt;       // tensor index space of ltr_head_create: ln_w, ln_b, then (W, b) per layer
+  ltr_head_encoder_desc enc{};        // n_blocks == 0: no encoder
+  int dm = 0;                         // d_model: the output layer's input width
+  int nm = 0;                         // matrices: the n dense layers, then QKV, W_o, w_1, w_2 of every encoder block
+  int in[HT_MAX_MATS], out[HT_MAX_MATS];
+  int mt[HT_MAX_MATS];                // tensor index of a matrix; its bias follows it
+  std::vector<size_t> off, cnt;       // tensor index space of the create call: ln_w, ln_b, (W, b) per layer, then the encoder's
+  std::vector<int> mat_of;            // matrix of a tensor, or -1
   size_t total = 0;
   float *P = nullptr, *G = nullptr, *M1 = nullptr, *V1 = nullptr;
-  __half* img[HT_MAX_LAYERS] = {};    // hi | lo planes of W  [ceil64(out)][ceil64(in)]
-  __half* imgT[HT_MAX_LAYERS] = {};   // hi | lo planes of W^T [ceil64(in)][ceil64(out)]
-  float* wamax = nullptr;             // [n][HT_AMAX_NB] first-stage maxima the images were scaled by
+  __half* img[HT_MAX_MATS] = {};      // hi | lo planes of W  [ceil64(out)][ceil64(in)]
+  __half* imgT[HT_MAX_MATS] = {};     // hi | lo planes of W^T [ceil64(in)][ceil64(out)]
+  float* wamax = nullptr;             // [nm][HT_AMAX_NB] first-stage maxima the images were scaled by
   long adam_step = 0;
+  int enc_tensor(int b, int i) const { return 2 + 2 * n + HT_ENC_PER_BLOCK * b + i; }   // b == n_blocks: the final norm
   ~ltr_head_trainer() {
     (void)hipFree(P); (void)hipFree(G); (void)hipFree(M1); (void)hipFree(V1); (void)hipFree(wamax);
-    for (int i = 0; i < HT_MAX_LAYERS; ++i) { (void)hipFree(img[i]); (void)hipFree(imgT[i]); }
+    for (int i = 0; i < HT_MAX_MATS; ++i) { (void)hipFree(img[i]); (void)hipFree(imgT[i]); }
   }
 };
 
@@ -619,10 +644,14 @@ int dw_parts(const ltr_head_trainer* t, int l, int M) {
   return tiles >= HT_DW_WIDE ? 1 : (M + HT_DW_PART - 1) / HT_DW_PART;
 }
 
+struct EncWs { float *qkv, *att, *lse, *zmid, *st1, *Z1, *A1; };     // what a block's backward reads again
 struct HtWs {
   float *stats, *rowmax, *scores, *dscore, *row_loss, *amax, *dw_part, *sq_part, *slots;
   double* cs_part;
-  float *Z[HT_MAX_LAYERS], *A[HT_MAX_LAYERS], *dz[2];
+  float *Z[HT_MAX_LAYERS], *A[HT_MAX_LAYERS], *dz[3];
+  EncWs e[HT_ENC_BLOCKS];
+  float *ez[HT_ENC_BLOCKS + 1], *est[HT_ENC_BLOCKS + 1];   // residual stream entering block b (b == n_blocks: leaving the last) and its row statistics
+  float *etmp, *eD;                                        // a sublayer's branch output [M, d_model]; D of the attention backward [h, M]
   void* ndcg; size_t ndcg_bytes;
   size_t bytes;
 };
@@ -634,15 +663,29 @@ HtWs carve(const ltr_head_trainer* t, int B, int S, void* base) {
   HtWs w;
   w.stats = take(M * 2 * 4); w.rowmax = take(M * 4); w.scores = take(M * 4); w.dscore = take(M * 4);
   w.row_loss = take((size_t)std::max(B, 1) * 4);
-  w.amax = take((size_t)(2 * t->n + 1) * HT_AMAX_NB * 4);
+  w.amax = take((size_t)(2 * t->nm + 2) * HT_AMAX_NB * 4);
   size_t maxw = t->d.input_norm ? t->d.n_features : 1, dwp = 1;
-  for (int l = 0; l < t->n; ++l) {
-    w.Z[l] = take(M * t->out[l] * 4); w.A[l] = take(M * t->out[l] * 4);
+  for (int l = 0; l < t->nm; ++l) {
+    if (l < t->n) { w.Z[l] = take(M * t->out[l] * 4); w.A[l] = take(M * t->out[l] * 4); }
     maxw = std::max<size_t>(maxw, t->out[l]);
     const int parts = dw_parts(t, l, (int)M);
     if (parts > 1) dwp = std::max(dwp, (size_t)parts * t->out[l] * t->in[l]);
   }
-  w.dz[0] = take(M * maxw * 4); w.dz[1] = take(M * maxw * 4);
+  const int nb = t->enc.n_blocks;
+  const size_t dm = t->dm;
+  if (nb) maxw = std::max(maxw, dm);
+  for (int b = 0; b < nb; ++b) {
+    EncWs& e = w.e[b];
+    e.qkv = take(M * 3 * dm * 4); e.att = take(M * dm * 4); e.lse = take(M * t->enc.h * 4);
+    e.zmid = take(M * dm * 4); e.st1 = take(M * 2 * 4);
+    e.Z1 = take(M * t->enc.d_ff * 4); e.A1 = take(M * t->enc.d_ff * 4);
+  }
+  for (int b = 0; nb && b <= nb; ++b) {
+    w.ez[b] = b == 0 && t->n > 1 ? w.A[t->n - 2] : take(M * dm * 4);
+    w.est[b] = take(M * 2 * 4);
+  }
+  w.etmp = take(nb ? M * dm * 4 : 0); w.eD = take(nb ? M * t->enc.h * 4 : 0);
+  w.dz[0] = take(M * maxw * 4); w.dz[1] = take(M * maxw * 4); w.dz[2] = take(nb ? M * maxw * 4 : 0);
   w.cs_part = (double*)take((M + HT_CS_PART - 1) / HT_CS_PART * maxw * 8);
   w.dw_part = take(dwp * 4);
   w.sq_part = take(HT_SQ_NB * 4);
@@ -654,6 +697,8 @@ HtWs carve(const ltr_head_trainer* t, int B, int S, void* base) {
   return w;
 }
 
+template <typename T> constexpr int hid_of() { return sizeof(T) == 4 ? LTR_HID_F32 : std::is_same<T, __half>::value ? LTR_HID_F16 : LTR_HID_BF16; }
+
 XSrc plain_src(const float* x, int K, const float* amax) {
   XSrc s{};
   s.x = x; s.amax = amax; s.K = K; s.vec = K % 16 == 0 && al16(x);
@@ -662,9 +707,9 @@ XSrc plain_src(const float* x, int K, const float* amax) {
 
 // the matrix of layer l: max|W| (first stage), then Adam and / or the image refresh
 int refresh_matrix(ltr_head_trainer* t, int l, const AdamArgs& a, int update, hipStream_t s) {
-  const size_t off = t->off[2 + 2 * l];
+  const size_t off = t->off[t->mt[l]];
   float* am = t->wamax + (size_t)l * HT_AMAX_NB;
-  ht_amax_kernel<<<HT_AMAX_NB, HT_THREADS, 0, s>>>(t->P + off, t->cnt[2 + 2 * l], am);
+  ht_amax_kernel<<<HT_AMAX_NB, HT_THREADS, 0, s>>>(t->P + off, t->cnt[t->mt[l]], am);
   LTR_LAUNCH_CHECK();
   ht_adam_tile_kernel<<<dim3(ceil64(t->in[l]) / 64, ceil64(t->out[l]) / 64), HT_THREADS, 0, s>>>(
       t->P + off, t->G + off, t->M1 + off, t->V1 + off, t->out[l], t->in[l], a, update, am, t->img[l], t->imgT[l]);
@@ -675,40 +720,76 @@ int refresh_matrix(ltr_head_trainer* t, int l, const AdamArgs& a, int update, hi
 template <typename T>
 int run_step(ltr_head_trainer* t, XSrc x0, int B, int S, const float* y_true, const int32_t* shuffle, int apply_update,
              float* loss_out, float* scores_out, float* grad_norm_out, const HtWs& w, hipStream_t s) {
-  const int M = B * S, n = t->n;
+  const int M = B * S, n = t->n, nm = t->nm, nb = t->enc.n_blocks, dm = t->dm;
   const bool norm = t->d.input_norm != 0;
   float* am_x0 = w.amax;
+  // first-stage maxima: of A[l] (dense layer l's output), for an encoder matrix of its own plain input; of dZ at matrix l's output
   auto am_A = [&](int l) { return w.amax + (size_t)(1 + l) * HT_AMAX_NB; };
-  auto am_dz = [&](int l) { return w.amax + (size_t)(1 + n + l) * HT_AMAX_NB; };
+  auto am_dz = [&](int l) { return w.amax + (size_t)(1 + nm + l) * HT_AMAX_NB; };
+  float* am_do = w.amax + (size_t)(1 + 2 * nm) * HT_AMAX_NB;
   const unsigned mt = (unsigned)((M + 63) / 64), cparts = (unsigned)((M + HT_CS_PART - 1) / HT_CS_PART);
+  const float* mask = t->cfg.loss == LTR_HEAD_LOSS_GIVEN ? nullptr : y_true;      // allRank's src_mask: y_true == pad_value
+  int rc = LTR_OK;
+
+  auto amax = [&](const float* x, size_t cnt, float* part) -> int {
+    ht_amax_kernel<<<HT_AMAX_NB, HT_THREADS, 0, s>>>(x, cnt, part);
+    LTR_LAUNCH_CHECK();
+    return LTR_OK;
+  };
+  // Z = a W_l^T + b_l, A = act(Z); `first`: a is the call's rows (of T)
+  auto forward = [&](int l, const XSrc& a, float* Z, float* A, int act, bool first) -> int {
+    ImgArgs g{};
+    g.a = a;
+    g.img = t->img[l]; g.ld = ceil64(t->in[l]); g.plane = (size_t)ceil64(t->out[l]) * g.ld;
+    g.img_amax = t->wamax + (size_t)l * HT_AMAX_NB;
+    g.bias = t->P + t->off[t->mt[l] + 1];
+    g.Z = Z; g.A = A;
+    g.M = M; g.N = t->out[l]; g.K = t->in[l];
+    g.act = act;
+    g.mode = HT_MODE_FWD;
+    const dim3 grid(mt, (unsigned)(ceil64(g.N) / 64));
+    if (first) ht_gemm_img_kernel<T><<<grid, HT_THREADS, 0, s>>>(g);
+    else ht_gemm_img_kernel<float><<<grid, HT_THREADS, 0, s>>>(g);
+    LTR_LAUNCH_CHECK();
+    return LTR_OK;
+  };
+  // a row-major f32 tensor under allRank's LayerNorm, applied on load from the statistics of enc_rows_kernel
+  auto normed = [&](const float* z, const float* stats, int tensor) {
+    XSrc a = plain_src(z, dm, nullptr);
+    a.stats = stats; a.ln_w = t->P + t->off[tensor]; a.ln_b = t->P + t->off[tensor + 1];
+    return a;
+  };
 
   // ---- forward
   x0.stats = w.stats;
   ht_rows_kernel<T><<<(M + 3) / 4, HT_THREADS, 0, s>>>(x0, M, w.stats, w.rowmax);
   LTR_LAUNCH_CHECK();
   if (!norm) {
-    ht_amax_kernel<<<HT_AMAX_NB, HT_THREADS, 0, s>>>(w.rowmax, (size_t)M, am_x0);
-    LTR_LAUNCH_CHECK();
+    if ((rc = amax(w.rowmax, (size_t)M, am_x0))) return rc;
     x0.amax = am_x0;
   }
-  for (int l = 0; l < n; ++l) {
-    ImgArgs g{};
-    g.a = l == 0 ? x0 : plain_src(w.A[l - 1], t->in[l], am_A(l - 1));
-    g.img = t->img[l]; g.ld = ceil64(t->in[l]); g.plane = (size_t)ceil64(t->out[l]) * g.ld;
-    g.img_amax = t->wamax + (size_t)l * HT_AMAX_NB;
-    g.bias = t->P + t->off[3 + 2 * l];
-    g.Z = w.Z[l]; g.A = w.A[l];
-    g.M = M; g.N = t->out[l]; g.K = t->in[l];
-    g.act = l == n - 1 ? t->d.output_activation : t->d.activation;
-    g.mode = HT_MODE_FWD;
-    const dim3 grid(mt, (unsigned)(ceil64(g.N) / 64));
-    if (l == 0) ht_gemm_img_kernel<T><<<grid, HT_THREADS, 0, s>>>(g);
-    else ht_gemm_img_kernel<float><<<grid, HT_THREADS, 0, s>>>(g);
-    LTR_LAUNCH_CHECK();
-    if (l < n - 1) {
-      ht_amax_kernel<<<HT_AMAX_NB, HT_THREADS, 0, s>>>(w.A[l], (size_t)M * t->out[l], am_A(l));
-      LTR_LAUNCH_CHECK();
+  auto dense_src = [&](int l) { return l == 0 ? x0 : plain_src(w.A[l - 1], t->in[l], am_A(l - 1)); };
+  for (int l = 0; l < (nb ? n - 1 : n); ++l) {
+    if ((rc = forward(l, dense_src(l), w.Z[l], w.A[l], l == n - 1 ? t->d.output_activation : t->d.activation, l == 0))) return rc;
+    if (l < n - 1 && (rc = amax(w.A[l], (size_t)M * t->out[l], am_A(l)))) return rc;
+  }
+  if (nb) {       // Encoder.forward (transformer.py:44-72): per block z += W_o MHA(norm(z)); z += w_2 relu(w_1 norm(z)); then norm
+    if (n == 1 && (rc = launch_enc_gather(x0.x, x0.res, hid_of<T>(), x0.row_index, M, dm, w.ez[0], s))) return rc;
+    if ((rc = launch_enc_rows(w.ez[0], nullptr, nullptr, M, dm, w.est[0], s))) return rc;
+    for (int b = 0; b < nb; ++b) {
+      const EncWs& e = w.e[b];
+      const int m0 = n + 4 * b;
+      if ((rc = forward(m0, normed(w.ez[b], w.est[b], t->enc_tensor(b, 0)), e.qkv, e.qkv, ACT_NONE, false))) return rc;
+      if ((rc = launch_enc_attn_fwd(e.qkv, mask, t->cfg.pad_value, B, S, dm, t->enc.h, e.att, e.lse, s))) return rc;
+      if ((rc = amax(e.att, (size_t)M * dm, am_A(m0 + 1)))) return rc;
+      if ((rc = forward(m0 + 1, plain_src(e.att, dm, am_A(m0 + 1)), w.etmp, w.etmp, ACT_NONE, false))) return rc;
+      if ((rc = launch_enc_rows(w.ez[b], w.etmp, e.zmid, M, dm, e.st1, s))) return rc;
+      if ((rc = forward(m0 + 2, normed(e.zmid, e.st1, t->enc_tensor(b, 6)), e.Z1, e.A1, ACT_RELU, false))) return rc;
+      if ((rc = amax(e.A1, (size_t)M * t->enc.d_ff, am_A(m0 + 3)))) return rc;
+      if ((rc = forward(m0 + 3, plain_src(e.A1, t->enc.d_ff, am_A(m0 + 3)), w.etmp, w.etmp, ACT_NONE, false))) return rc;
+      if ((rc = launch_enc_rows(e.zmid, w.etmp, w.ez[b + 1], M, dm, w.est[b + 1], s))) return rc;
     }
+    if ((rc = forward(n - 1, normed(w.ez[nb], w.est[nb], t->enc_tensor(nb, 0)), w.Z[n - 1], w.A[n - 1], t->d.output_activation, false))) return rc;
   }
   const int dout = t->out[n - 1];
   ht_score_kernel<<<blocks(M), HT_THREADS, 0, s>>>(w.A[n - 1], M, dout, w.scores, scores_out);
@@ -716,7 +797,6 @@ int run_step(ltr_head_trainer* t, XSrc x0, int B, int S, const float* y_true, co
 
   // ---- loss on the [B, S] scores -> dLoss / dscore
   const float* dscore = w.dscore;
-  int rc = LTR_OK;
   switch (t->cfg.loss) {
     case LTR_LOSS_LISTMLE:
       rc = ltr_listmle(w.scores, y_true, shuffle, B, S, t->cfg.listmle_eps, t->cfg.pad_value, loss_out, w.row_loss, w.dscore, s);
@@ -739,50 +819,112 @@ int run_step(ltr_head_trainer* t, XSrc x0, int B, int S, const float* y_true, co
   ht_out_grad_kernel<<<blocks((size_t)M * dout), HT_THREADS, 0, s>>>(dscore, w.Z[n - 1], (size_t)M * dout, dout,
                                                                     t->d.output_activation, w.dz[(n - 1) & 1]);
   LTR_LAUNCH_CHECK();
-  for (int l = n - 1; l >= 0; --l) {
+  // the bias and weight gradients of matrix l from dZ [M, out] at its output and from its input
+  auto param_grads = [&](int l, const float* dz, const XSrc& in, bool first) -> int {
     const int O = t->out[l], K = t->in[l];
-    float* dz = w.dz[l & 1];
+    float* gw = t->G + t->off[t->mt[l]];
     ht_amax_kernel<<<HT_AMAX_NB, HT_THREADS, 0, s>>>(dz, (size_t)M * O, am_dz(l));
     LTR_LAUNCH_CHECK();
     ht_colsum_kernel<<<dim3((unsigned)((O + 63) / 64), cparts), HT_THREADS, 0, s>>>(dz, M, O, w.cs_part);
     LTR_LAUNCH_CHECK();
-    ht_colparts_sum_kernel<<<blocks(O), HT_THREADS, 0, s>>>(w.cs_part, (int)cparts, O, t->G + t->off[3 + 2 * l]);
+    ht_colparts_sum_kernel<<<blocks(O), HT_THREADS, 0, s>>>(w.cs_part, (int)cparts, O, t->G + t->off[t->mt[l] + 1]);
     LTR_LAUNCH_CHECK();
     const int parts = dw_parts(t, l, M);
     DwArgs dw{};
     dw.a = plain_src(dz, O, am_dz(l));
-    dw.b = l == 0 ? x0 : plain_src(w.A[l - 1], K, am_A(l - 1));
-    dw.out = parts > 1 ? w.dw_part : t->G + t->off[2 + 2 * l];
+    dw.b = in;
+    dw.out = parts > 1 ? w.dw_part : gw;
     dw.M = M; dw.O = O; dw.K = K; dw.part_rows = parts > 1 ? HT_DW_PART : M;
     const dim3 grid((unsigned)((O + 63) / 64), (unsigned)((K + 63) / 64), (unsigned)parts);
-    if (l == 0) ht_gemm_dw_kernel<T><<<grid, HT_THREADS, 0, s>>>(dw);
+    if (first) ht_gemm_dw_kernel<T><<<grid, HT_THREADS, 0, s>>>(dw);
     else ht_gemm_dw_kernel<float><<<grid, HT_THREADS, 0, s>>>(dw);
     LTR_LAUNCH_CHECK();
     if (parts > 1) {
-      ht_parts_sum_kernel<<<blocks((size_t)O * K), HT_THREADS, 0, s>>>(w.dw_part, parts, (size_t)O * K, t->G + t->off[2 + 2 * l]);
+      ht_parts_sum_kernel<<<blocks((size_t)O * K), HT_THREADS, 0, s>>>(w.dw_part, parts, (size_t)O * K, gw);
       LTR_LAUNCH_CHECK();
     }
-    if (l == 0 && !norm) break;
-    ImgArgs g{};                                  // dA_{l-1} = dZ_l W_l, times act'(Z_{l-1}); layer 0: the gradient at the LayerNorm output
-    g.a = dw.a;
+    return LTR_OK;
+  };
+  // out = dZ W_l, times act'(Zprev) where Zprev is given; after param_grads(l, dz)
+  auto input_grad = [&](int l, const float* dz, const float* Zprev, int act, float* out) -> int {
+    const int O = t->out[l], K = t->in[l];
+    ImgArgs g{};
+    g.a = plain_src(dz, O, am_dz(l));
     g.img = t->imgT[l]; g.ld = ceil64(O); g.plane = (size_t)ceil64(K) * g.ld;
     g.img_amax = t->wamax + (size_t)l * HT_AMAX_NB;
-    g.Zprev = l > 0 ? w.Z[l - 1] : nullptr;
-    g.out = w.dz[(l + 1) & 1];
-    g.M = M; g.N = K; g.K = O; g.act = t->d.activation; g.mode = HT_MODE_DX;
+    g.Zprev = Zprev;
+    g.out = out;
+    g.M = M; g.N = K; g.K = O; g.act = act; g.mode = HT_MODE_DX;
     ht_gemm_img_kernel<float><<<dim3(mt, (unsigned)(ceil64(K) / 64)), HT_THREADS, 0, s>>>(g);
     LTR_LAUNCH_CHECK();
-    if (l == 0) {                                 // d beta = column sums of g, d gamma = column sums of g * xhat
-      const dim3 cg((unsigned)((K + 63) / 64), cparts);
-      ht_colsum_kernel<<<cg, HT_THREADS, 0, s>>>(g.out, M, K, w.cs_part);
+    return LTR_OK;
+  };
+  // a LayerNorm's d beta = column sums of g and d gamma = column sums of g * xhat, g the gradient at its output
+  auto norm_grads = [&](const XSrc& in, const float* g, int tensor, bool first) -> int {
+    const int K = in.K;
+    const dim3 cg((unsigned)((K + 63) / 64), cparts);
+    if (tensor == t->enc_tensor(nb, 0) && nb) {      // the encoder's final norm
+      const int ot = t->mt[n - 1];
+      ht_matvec_t_kernel<<<blocks(K), HT_THREADS, 0, s>>>(t->P + t->off[ot], t->G + t->off[ot + 1], dout, K, t->G + t->off[tensor + 1]);
+    } else {
+      ht_colsum_kernel<<<cg, HT_THREADS, 0, s>>>(g, M, K, w.cs_part);
       LTR_LAUNCH_CHECK();
-      ht_colparts_sum_kernel<<<blocks(K), HT_THREADS, 0, s>>>(w.cs_part, (int)cparts, K, t->G + t->off[1]);
-      LTR_LAUNCH_CHECK();
-      ht_lnw_kernel<T><<<cg, HT_THREADS, 0, s>>>(x0, g.out, M, w.cs_part);
-      LTR_LAUNCH_CHECK();
-      ht_colparts_sum_kernel<<<blocks(K), HT_THREADS, 0, s>>>(w.cs_part, (int)cparts, K, t->G + t->off[0]);
+      ht_colparts_sum_kernel<<<blocks(K), HT_THREADS, 0, s>>>(w.cs_part, (int)cparts, K, t->G + t->off[tensor + 1]);
+    }
+    LTR_LAUNCH_CHECK();
+    if (first) ht_lnw_kernel<T><<<cg, HT_THREADS, 0, s>>>(in, g, M, w.cs_part);
+    else ht_lnw_kernel<float><<<cg, HT_THREADS, 0, s>>>(in, g, M, w.cs_part);
+    LTR_LAUNCH_CHECK();
+    ht_colparts_sum_kernel<<<blocks(K), HT_THREADS, 0, s>>>(w.cs_part, (int)cparts, K, t->G + t->off[tensor]);
+    LTR_LAUNCH_CHECK();
+    return LTR_OK;
+  };
+
+  if (nb) {
+    // the output layer reads norm(z); R = dz[2] carries the gradient at the residual stream down the blocks, dz[0] and dz[1]
+    // hold in turn dZ_1 / dO / the gradient at a norm's output and dQ|dK|dV
+    float *R = w.dz[2], *t0 = w.dz[0], *t1 = w.dz[1];
+    const float* dzo = w.dz[(n - 1) & 1];
+    float* dy = w.dz[n & 1];
+    XSrc in = normed(w.ez[nb], w.est[nb], t->enc_tensor(nb, 0));
+    if ((rc = param_grads(n - 1, dzo, in, false))) return rc;
+    if ((rc = input_grad(n - 1, dzo, nullptr, ACT_NONE, dy))) return rc;
+    if ((rc = norm_grads(in, dy, t->enc_tensor(nb, 0), false))) return rc;
+    if ((rc = launch_enc_ln_bwd(w.ez[nb], w.est[nb], in.ln_w, dy, nullptr, R, M, dm, s))) return rc;
+    for (int b = nb - 1; b >= 0; --b) {
+      const EncWs& e = w.e[b];
+      const int m0 = n + 4 * b;
+      // z_out = z_mid + w_2 relu(w_1 norm(z_mid))
+      if ((rc = param_grads(m0 + 3, R, plain_src(e.A1, t->enc.d_ff, am_A(m0 + 3)), false))) return rc;
+      if ((rc = input_grad(m0 + 3, R, e.Z1, ACT_RELU, t0))) return rc;
+      in = normed(e.zmid, e.st1, t->enc_tensor(b, 6));
+      if ((rc = param_grads(m0 + 2, t0, in, false))) return rc;
+      if ((rc = input_grad(m0 + 2, t0, nullptr, ACT_NONE, t1))) return rc;
+      if ((rc = norm_grads(in, t1, t->enc_tensor(b, 6), false))) return rc;
+      if ((rc = launch_enc_ln_bwd(e.zmid, e.st1, in.ln_w, t1, R, R, M, dm, s))) return rc;
+      // z_mid = z + W_o MHA(norm(z))
+      if ((rc = param_grads(m0 + 1, R, plain_src(e.att, dm, am_A(m0 + 1)), false))) return rc;
+      if ((rc = input_grad(m0 + 1, R, nullptr, ACT_NONE, t0))) return rc;
+      if ((rc = amax(t0, (size_t)M * dm, am_do))) return rc;
+      if ((rc = launch_enc_attn_bwd(e.qkv, t0, e.lse, am_do, mask, t->cfg.pad_value, B, S, dm, t->enc.h, w.eD, t1, s))) return rc;
+      in = normed(w.ez[b], w.est[b], t->enc_tensor(b, 0));
+      if ((rc = param_grads(m0, t1, in, false))) return rc;
+      if ((rc = input_grad(m0, t1, nullptr, ACT_NONE, t0))) return rc;
+      if ((rc = norm_grads(in, t0, t->enc_tensor(b, 0), false))) return rc;
+      if ((rc = launch_enc_ln_bwd(w.ez[b], w.est[b], in.ln_w, t0, R, R, M, dm, s))) return rc;
+    }
+    if (n > 1) {      // R is the gradient at A_{n-2}: dZ_{n-2} = R act'(Z_{n-2})
+      ht_out_grad_kernel<<<blocks((size_t)M * dm), HT_THREADS, 0, s>>>(R, w.Z[n - 2], (size_t)M * dm, 1, t->d.activation, w.dz[(n - 2) & 1]);
       LTR_LAUNCH_CHECK();
     }
+  }
+  for (int l = nb ? n - 2 : n - 1; l >= 0; --l) {
+    float* dz = w.dz[l & 1];
+    if ((rc = param_grads(l, dz, dense_src(l), l == 0))) return rc;
+    if (l == 0 && !norm) break;
+    // dA_{l-1} = dZ_l W_l, times act'(Z_{l-1}); layer 0: the gradient at the LayerNorm output
+    if ((rc = input_grad(l, dz, l > 0 ? w.Z[l - 1] : nullptr, t->d.activation, w.dz[(l + 1) & 1]))) return rc;
+    if (l == 0 && (rc = norm_grads(x0, w.dz[1], 0, true))) return rc;
   }
 
   // ---- clip_grad_norm_ (train_utils.py:40-41)
@@ -803,7 +945,7 @@ int run_step(ltr_head_trainer* t, XSrc x0, int B, int S, const float* y_true, co
                    (float)(1.0 - std::pow(b1, (double)t->adam_step)), (float)(1.0 - std::pow(b2, (double)t->adam_step))};
   for (size_t i = 0; i < t->cnt.size(); ++i) {
     if (!t->cnt[i]) continue;
-    if (i >= 2 && i % 2 == 0) { if ((rc = refresh_matrix(t, (int)(i - 2) / 2, a, 1, s))) return rc; continue; }
+    if (t->mat_of[i] >= 0) { if ((rc = refresh_matrix(t, t->mat_of[i], a, 1, s))) return rc; continue; }
     const size_t o = t->off[i];
     ht_adam_vec_kernel<<<blocks(t->cnt[i]), HT_THREADS, 0, s>>>(t->P + o, t->G + o, t->M1 + o, t->V1 + o, t->cnt[i], a);
     LTR_LAUNCH_CHECK();
@@ -816,7 +958,8 @@ int run_step(ltr_head_trainer* t, XSrc x0, int B, int S, const float* y_true, co
 
 extern "C" {
 
-int ltr_head_train_create(const ltr_head_desc* d, const void* const* weights, int32_t n_weights,
+// both create calls; enc == nullptr: no encoder
+static int create_trainer(const ltr_head_desc* d, const ltr_head_encoder_desc* enc, const void* const* weights, int32_t n_weights,
                           const ltr_head_train_config* cfg, void* stream, ltr_head_train_handle* out) {
   if (!d || !weights || !cfg || !out) { set_error("ltr_head_train_create: NULL argument"); return LTR_E_INVAL; }
   if (d->n_fc < 0 || d->n_fc > 8 || d->n_features < 1 || d->n_features > 8192 || d->d_output < 1 || d->d_output > 8192) {
@@ -835,7 +978,18 @@ int ltr_head_train_create(const ltr_head_desc* d, const void* const* weights, in
     const int rc = ltr_lambdaloss(nullptr, nullptr, 0, 0, &cfg->lambda, nullptr, nullptr, nullptr, 0, nullptr);
     if (rc) return rc;
   }
-  const int want = 2 + 2 * (d->n_fc + 1);
+  const int dm = d->n_fc ? d->fc_sizes[d->n_fc - 1] : d->n_features, n_head = 2 + 2 * (d->n_fc + 1);
+  if (enc) {      // the checks of ltr_head_encoder_create
+    if (enc->positional_encoding != 0) { set_error("ltr_head_train_create_encoder: positional_encoding is not built"); return LTR_E_INVAL; }
+    if (enc->n_blocks < 1 || enc->n_blocks > HT_ENC_BLOCKS || enc->d_ff < 1 || enc->d_ff > 65536 || enc->h < 1) {
+      set_error("ltr_head_train_create_encoder: bad shape (N=%d d_ff=%d h=%d)", enc->n_blocks, enc->d_ff, enc->h); return LTR_E_INVAL;
+    }
+    if (dm < 2 || dm % enc->h != 0 || dm / enc->h % 16 != 0 || dm / enc->h > 128) {
+      set_error("ltr_head_train_create_encoder: d_model = %d, h = %d: d_k must be a multiple of 16 up to 128", dm, enc->h); return LTR_E_INVAL;
+    }
+    if (d->n_fc == 0 && d->input_norm) { set_error("ltr_head_train_create_encoder: an input norm needs an FC layer"); return LTR_E_INVAL; }
+  }
+  const int want = n_head + (enc ? HT_ENC_PER_BLOCK * enc->n_blocks + 2 : 0);
   if (n_weights != want) { set_error("ltr_head_train_create: %d weight pointers, expected %d", n_weights, want); return LTR_E_INVAL; }
   for (int i = 0; i < d->n_fc; ++i)
     if (d->fc_sizes[i] < 1 || d->fc_sizes[i] > 8192) { set_error("ltr_head_train_create: layer %d: bad size %d", i, d->fc_sizes[i]); return LTR_E_INVAL; }
@@ -851,8 +1005,25 @@ int ltr_head_train_create(const ltr_head_desc* d, const void* const* weights, in
     const int o = l < d->n_fc ? d->fc_sizes[l] : d->d_output;
     t->in[l] = in; t->out[l] = o;
     t->cnt[2 + 2 * l] = (size_t)o * in; t->cnt[3 + 2 * l] = (size_t)o;
+    t->mt[l] = 2 + 2 * l;
     in = o;
   }
+  t->nm = t->n; t->dm = dm;
+  if (enc) {
+    t->enc = *enc;
+    const int io[4][2] = {{dm, 3 * dm}, {dm, dm}, {dm, enc->d_ff}, {enc->d_ff, dm}};      // QKV, W_o, w_1, w_2
+    const int at[4] = {2, 4, 8, 10};
+    for (int b = 0; b <= enc->n_blocks; ++b)
+      for (int i = 0; i < (b < enc->n_blocks ? HT_ENC_PER_BLOCK : 2); ++i) t->cnt[t->enc_tensor(b, i)] = (size_t)dm;   // norms; the rest below
+    for (int b = 0; b < enc->n_blocks; ++b)
+      for (int i = 0; i < 4; ++i) {
+        const int l = t->nm++, ti = t->enc_tensor(b, at[i]);
+        t->in[l] = io[i][0]; t->out[l] = io[i][1]; t->mt[l] = ti;
+        t->cnt[ti] = (size_t)io[i][0] * io[i][1]; t->cnt[ti + 1] = (size_t)io[i][1];
+      }
+  }
+  t->mat_of.assign(want, -1);
+  for (int l = 0; l < t->nm; ++l) t->mat_of[t->mt[l]] = l;
   size_t total = 0;
   for (int i = 0; i < want; ++i) { t->off[i] = total; total += (t->cnt[i] + 63) / 64 * 64; }
   t->total = total;
@@ -867,8 +1038,8 @@ int ltr_head_train_create(const ltr_head_desc* d, const void* const* weights, in
   hipStream_t s = (hipStream_t)stream;
   bool ok = hipMalloc((void**)&t->P, total * 4) == hipSuccess && hipMalloc((void**)&t->G, total * 4) == hipSuccess &&
             hipMalloc((void**)&t->M1, total * 4) == hipSuccess && hipMalloc((void**)&t->V1, total * 4) == hipSuccess &&
-            hipMalloc((void**)&t->wamax, (size_t)t->n * HT_AMAX_NB * 4) == hipSuccess;
-  for (int l = 0; ok && l < t->n; ++l) {
+            hipMalloc((void**)&t->wamax, (size_t)t->nm * HT_AMAX_NB * 4) == hipSuccess;
+  for (int l = 0; ok && l < t->nm; ++l) {
     const size_t halves = (size_t)2 * ceil64(t->out[l]) * ceil64(t->in[l]);
     ok = hipMalloc((void**)&t->img[l], halves * 2) == hipSuccess && hipMalloc((void**)&t->imgT[l], halves * 2) == hipSuccess;
   }
@@ -879,13 +1050,24 @@ int ltr_head_train_create(const ltr_head_desc* d, const void* const* weights, in
     if (t->cnt[i] && hipMemcpyAsync(t->P + t->off[i], weights[i], t->cnt[i] * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
       delete t; set_error("ltr_head_train_create: copying weight %d failed", i); return LTR_E_HIP;
     }
-  for (int l = 0; l < t->n; ++l) {
+  for (int l = 0; l < t->nm; ++l) {
     const int rc = refresh_matrix(t, l, AdamArgs{}, 0, s);
     if (rc) { delete t; return rc; }
   }
   if (hipStreamSynchronize(s) != hipSuccess) { delete t; set_error("ltr_head_train_create: building the images failed"); return LTR_E_HIP; }
   *out = t;
   return LTR_OK;
+}
+
+int ltr_head_train_create(const ltr_head_desc* d, const void* const* weights, int32_t n_weights,
+                          const ltr_head_train_config* cfg, void* stream, ltr_head_train_handle* out) {
+  return create_trainer(d, nullptr, weights, n_weights, cfg, stream, out);
+}
+
+int ltr_head_train_create_encoder(const ltr_head_desc* d, const ltr_head_encoder_desc* enc, const void* const* weights,
+                                  int32_t n_weights, const ltr_head_train_config* cfg, void* stream, ltr_head_train_handle* out) {
+  if (!enc) { set_error("ltr_head_train_create_encoder: NULL argument"); return LTR_E_INVAL; }
+  return create_trainer(d, enc, weights, n_weights, cfg, stream, out);
 }
 
 int ltr_head_train_destroy(ltr_head_train_handle h) {
@@ -909,6 +1091,7 @@ int ltr_head_train_step(ltr_head_train_handle h, const void* hidden, const void*
     return LTR_E_INVAL;
   }
   if (B * S == 0) return LTR_OK;
+  if (h->enc.n_blocks && B > 65535) { set_error("ltr_head_train_step: the encoder takes at most 65535 slates (B = %d)", B); return LTR_E_INVAL; }
   const int loss = h->cfg.loss;
   if (!hidden || !y_true || !workspace || (loss != LTR_HEAD_LOSS_GIVEN && !loss_out)) { set_error("ltr_head_train_step: NULL argument"); return LTR_E_INVAL; }
   if (loss == LTR_LOSS_LISTMLE && (!shuffle || S > 4096)) { set_error("ltr_head_train_step: listMLE needs the shuffle permutation and S <= 4096"); return LTR_E_INVAL; }

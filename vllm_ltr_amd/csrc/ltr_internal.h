@@ -354,7 +354,25 @@ int launch_head_layers(const HeadModel* m, int li0, int li1, const void* x, cons
                        const int32_t* row_index, const float* ln_w, const float* ln_b, int norm_kind, int N, float* stats,
                        float* const buf[2], float* scores_out, hipStream_t s, const float** cur_out);
 
-// largest i in [0, n) with cu[i] <= t   (cu ascending, cu[0] <= t < cu[n])
+// z[r] = (hidden + residual)[row_index[r]] in f32, the sum rounded once to the rows' dtype (ltr_head_encoder.hip)
+int launch_enc_gather(const void* x, const void* res, int x_dtype, const int32_t* row_index, int N, int K, float* z,
+                      hipStream_t s);
+
+// ---- training of the slate encoder (ltr_head_encoder_train.hip), driven by ltr_head_train.hip ----
+// z_out = z + branch (branch nullptr: z_out is not written), stats[r] = (mean, 1 / (unbiased std + eps)) of the row
+int launch_enc_rows(const float* z, const float* branch, float* z_out, int M, int K, float* stats, hipStream_t s);
+// dx = d allRank-LayerNorm(x) / dx applied to dy, + resid (nullptr: none; dx may be resid)
+int launch_enc_ln_bwd(const float* x, const float* stats, const float* a2, const float* dy, const float* resid, float* dx,
+                      int M, int K, hipStream_t s);
+// qkv f32 [B S, 3 dm] -> out [B S, dm], lse [h, B S] (exp2 domain); key j of slate b is masked when y[b S + j] == pad
+// (y nullptr: no mask); a row with no valid key gets output 0
+int launch_enc_attn_fwd(const float* qkv, const float* y, float pad, int B, int S, int dm, int h, float* out, float* lse,
+                        hipStream_t s);
+// dqkv [B S, 3 dm] = (dQ | dK | dV) from dO [B S, dm]; am_do: the 64 first-stage maxima of |dO|; D: scratch [h, B S]
+int launch_enc_attn_bwd(const float* qkv, const float* dO, const float* lse, const float* am_do, const float* y, float pad,
+                        int B, int S, int dm, int h, float* D, float* dqkv, hipStream_t s);
+
+// largest i in [0, n) with cu[i] <= t  (cu ascending, cu[0] <= t < cu[n])
 __device__ __forceinline__ int find_request(const int32_t* __restrict__ cu, int n, int t) {
   int lo = 0, hi = n;  // answer in [lo, hi)
   while (hi - lo > 1) {

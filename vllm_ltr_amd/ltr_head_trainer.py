@@ -4,7 +4,11 @@ The reference only Xavier-initialises this head (``vllm/model_executor/predictor
 encoder-less copy of allRank's ``FCModel`` / ``OutputLayer`` / ``LTRModel`` (``train/allrank/models/model.py:28-166``),
 which allRank's loop trains (``train/allrank/training/train_utils.py:34-45``: loss, ``backward``, ``clip_grad_norm_``,
 ``opt.step``).  ``HipLTRHeadTrainer.step`` is one such step on stored hidden states; ``to_head`` hands the weights to
-``HipLTRHead``.  The state dict uses the reference's parameter names, as ``HipLTRHead`` does."""
+``HipLTRHead``.  The state dict uses the reference's parameter names, as ``HipLTRHead`` does.
+
+With ``transformer`` (``ModelConfig.transformer``) allRank's slate encoder is trained between the FC stack and the output
+layer (``ltr_head_train_create_encoder``): each row of the ``[B, S]`` labels is one slate, and an item whose label is
+``pad_value`` is masked as a key (``transformer.py:166-167``; not under loss ``"given"``, which has no labels)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -34,6 +38,38 @@ def _init_state(n_features: int, sizes: List[int], norm: bool, d_output: int) ->
     return sd
 
 
+def _init_encoder_state(d_model: int, cfg: dict) -> Dict[str, np.ndarray]:
+    """make_transformer (transformer.py:246-263): xavier_uniform_ on every matrix, torch's defaults on the biases; LayerNorm
+    starts at a_2 = 1, b_2 = 0 (:79-81)."""
+    sd = {}
+    for i in range(cfg["N"]):
+        p = f"encoder.layers.{i}."
+        dims = [(p + f"self_attn.linears.{j}", d_model, d_model) for j in range(4)]
+        dims += [(p + "feed_forward.w_1", d_model, cfg["d_ff"]), (p + "feed_forward.w_2", cfg["d_ff"], d_model)]
+        for name, fan_in, fan_out in dims:
+            lin = torch.nn.Linear(fan_in, fan_out)
+            torch.nn.init.xavier_uniform_(lin.weight)
+            sd[name + ".weight"] = lin.weight.detach().numpy().copy()
+            sd[name + ".bias"] = lin.bias.detach().numpy().copy()
+    for p in [f"encoder.layers.{i}.sublayer.{j}.norm." for i in range(cfg["N"]) for j in range(2)] + ["encoder.norm."]:
+        sd[p + "a_2"], sd[p + "b_2"] = np.ones(d_model, np.float32), np.zeros(d_model, np.float32)
+    return sd
+
+
+def _encoder_names(cfg: dict) -> list:
+    """The encoder's tensors in the order of ltr_head_encoder_create; a tuple names the three tensors stacked into one."""
+    names = []
+    for i in range(cfg["N"]):
+        p = f"encoder.layers.{i}."
+        qkv = lambda what: tuple(f"{p}self_attn.linears.{j}.{what}" for j in range(3))
+        names += [p + "sublayer.0.norm.a_2", p + "sublayer.0.norm.b_2", qkv("weight"), qkv("bias"),
+                  p + "self_attn.linears.3.weight", p + "self_attn.linears.3.bias",
+                  p + "sublayer.1.norm.a_2", p + "sublayer.1.norm.b_2",
+                  p + "feed_forward.w_1.weight", p + "feed_forward.w_1.bias",
+                  p + "feed_forward.w_2.weight", p + "feed_forward.w_2.bias"]
+    return names + ["encoder.norm.a_2", "encoder.norm.b_2"]
+
+
 class HipLTRHeadTrainer:
     def __init__(self, n_features: int, fc_model: Optional[dict], post_model: dict,
                  state: Optional[Dict[str, np.ndarray]] = None, lr: float = 1e-3, weight_decay: float = 0.0,
@@ -42,9 +78,9 @@ class HipLTRHeadTrainer:
                  pad_value: float = PADDED_Y_VALUE, transformer: Optional[dict] = None, loss_args: Optional[dict] = None):
         """``loss_args``: allRank's ``loss.args`` of ``"lambdaLoss"`` (lambdaLoss.py:23-24: weighing_scheme, k, sigma, mu, reduction,
         reduction_log, eps, padded_value_indicator); eps and the padding value default to ``listmle_eps`` and ``pad_value``."""
-        if transformer:
-            raise NotImplementedError("HipLTRHeadTrainer: training the slate encoder (ModelConfig.transformer) is not built; "
-                                      "HipLTRHead scores a checkpoint that allRank trained with one")
+        if transformer and (transformer.get("dropout") or transformer.get("positional_encoding") is not None):
+            raise NotImplementedError("HipLTRHeadTrainer: the slate encoder is trained without dropout and without "
+                                      "positional encoding; neither is built")
         if fc_model and fc_model.get("dropout"):
             raise NotImplementedError("HipLTRHeadTrainer: FCModel's dropout is not built (the device training step covers "
                                       "the dense layers, the input LayerNorm and the six activations)")
@@ -62,17 +98,22 @@ class HipLTRHeadTrainer:
         self.lib = _lib.load()
         self.device = torch.device(device)
         self.n_features, self.fc_model, self.post_model, self.loss = n_features, fc_model, post_model, loss
+        self.transformer = transformer
         sizes = list(fc_model["sizes"]) if fc_model else []
         norm = bool(fc_model and fc_model.get("input_norm"))
         if state is None:
             state = _init_state(n_features, sizes, norm, post_model["d_output"])
+            if transformer:
+                state.update(_init_encoder_state(sizes[-1] if sizes else n_features, transformer))
         self._names = (["input_layer.input_norm.weight", "input_layer.input_norm.bias"] if norm else [None, None])
         for i in range(len(sizes)):
             self._names += [f"input_layer.layers.{i}.weight", f"input_layer.layers.{i}.bias"]
         self._names += ["output_layer.w_1.weight", "output_layer.w_1.bias"]
-        self._shapes = {k: tuple(np.shape(state[k])) for k in self._names if k}
-        t = [torch.from_numpy(np.asarray(state[k]).astype(np.float32)).to(self.device).contiguous() if k else None
-             for k in self._names]
+        if transformer:
+            self._names += _encoder_names(transformer)
+        self._shapes = {k: tuple(np.shape(state[k])) for ks in self._names if ks for k in ([ks] if isinstance(ks, str) else ks)}
+        stacked = lambda ks: np.asarray(state[ks]) if isinstance(ks, str) else np.concatenate([np.asarray(state[k]) for k in ks], 0)
+        t = [torch.from_numpy(stacked(ks).astype(np.float32)).to(self.device).contiguous() if ks else None for ks in self._names]
         desc = _lib.HeadDesc()
         desc.n_features, desc.n_fc = n_features, len(sizes)
         for i, s in enumerate(sizes):
@@ -87,8 +128,13 @@ class HipLTRHeadTrainer:
         ptrs = (C.c_void_p * len(t))(*[(x.data_ptr() if x is not None else None) for x in t])
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.ltr_head_train_create(C.byref(desc), ptrs, len(t), C.byref(cfg), self._stream(),
-                                                      C.byref(self._h)), "ltr_head_train_create")
+            if transformer:
+                enc = _lib.HeadEncoderDesc(transformer["N"], transformer["d_ff"], transformer["h"], 0)
+                _lib.check(self.lib.ltr_head_train_create_encoder(C.byref(desc), C.byref(enc), ptrs, len(t), C.byref(cfg),
+                                                                  self._stream(), C.byref(self._h)), "ltr_head_train_create_encoder")
+            else:
+                _lib.check(self.lib.ltr_head_train_create(C.byref(desc), ptrs, len(t), C.byref(cfg), self._stream(),
+                                                          C.byref(self._h)), "ltr_head_train_create")
         self._ws = None                      # grows, never shrinks
         self.scores: Optional[torch.Tensor] = None       # [B, S] of the last step, before its update
         self.grad_norm: Optional[torch.Tensor] = None    # [1] global L2 norm of the last step's gradients, before clipping
@@ -150,7 +196,8 @@ class HipLTRHeadTrainer:
             t = torch.empty(n.value, dtype=torch.float32, device=self.device)
             _lib.check(self.lib.ltr_head_train_read(self._h, i, what, t.data_ptr(), n.value, C.byref(n), self._stream()),
                        "ltr_head_train_read")
-            out[name] = t.view(self._shapes[name])
+            for k, part in zip([name] if isinstance(name, str) else name, [t] if isinstance(name, str) else t.chunk(3)):
+                out[k] = part.view(self._shapes[k])
         return out
 
     def gradients(self) -> Dict[str, np.ndarray]:
@@ -162,11 +209,16 @@ class HipLTRHeadTrainer:
 
     def to_head(self, weight_dtype: str = "f16") -> HipLTRHead:
         return HipLTRHead(self.n_features, self.fc_model, self.post_model, self.state_dict(), device=str(self.device),
-                          weight_dtype=weight_dtype)
+                          weight_dtype=weight_dtype, transformer=self.transformer)
 
     def evaluate(self, hidden: torch.Tensor, labels: torch.Tensor) -> float:
         """Kendall's tau-b of the labels and the current head's scores (train/trainer.py:195); the predictions stay on the
-        device.  f32 hidden states are scored with the f32 weights, fp16 / bf16 ones as deployed (fp16 weights)."""
-        head = self.to_head("f32" if hidden.dtype == torch.float32 else "f16")
-        pred = head.score(hidden)
+        device.  f32 hidden states are scored with the f32 weights, fp16 / bf16 ones as deployed (fp16 weights); the encoder
+        always scores with fp16 weights, each row of the [B, S] labels as one slate."""
+        head = self.to_head("f32" if hidden.dtype == torch.float32 and not self.transformer else "f16")
+        if self.transformer:
+            B, S = labels.shape
+            pred = head.score(hidden, cu_slates=torch.arange(0, B * S + 1, S, dtype=torch.int32, device=self.device), max_slate=S)
+        else:
+            pred = head.score(hidden)
         return metrics.kendall_tau(labels.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous(), pred)
