@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LTR_ABI_VERSION 13
+#define LTR_ABI_VERSION 14
 
 enum {
   LTR_OK = 0,
@@ -477,6 +477,44 @@ typedef struct ltr_order_agreement_result {
 size_t ltr_order_agreement_workspace_bytes(int64_t n);
 int ltr_order_agreement(const float* x, const float* y, int32_t n, ltr_order_agreement_result* result_out,
                         void* workspace, size_t ws_bytes, void* stream);
+
+/* Slate metrics of allRank's epoch end (ABI 14; DESIGN.md 4.9 "Slate metrics"): ndcg, dcg and mrr of
+ * train/allrank/models/metrics.py:65-171 at a list of cut-offs, and their means over the slates as
+ * train/allrank/training/train_utils.py:48-72 forms them (compute_metrics -> metric_on_epoch; :115-147 reads config.val_metric
+ * from that result for ReduceLROnPlateau and early stopping).  y_pred, y_true f32 [B, S] row-major, 1 <= S <= 4096, 1 <= B <= 2^20,
+ * 1 <= n_ats <= 8.  Per slate:
+ *    1 padding    item i is padded when y_true[i] == pad_value; its score counts as -inf and its label as 0 (metrics.py:89-96)
+ *    2 order      position r = 0, 1, ... runs over ALL S items under descending score; equal scores: the lower index first
+ *                 (torch.sort leaves this open); -0 equals +0; a NaN score sorts before everything (where torch.sort puts it)
+ *    3 gain       2^l - 1 (gain 0) or l (gain 1), in f32
+ *    4 discount   disc[r] = 1 / log2(r + 2) in f32
+ *    5 dcg[j]     sum over r < min(ats[j], S) of gain(label at position r) disc[r]
+ *    6 idcg[j]    the same sum with the items ordered by descending label, padded items counting as 0
+ *    7 ndcg[j]    dcg[j] / idcg[j], or filler_value where idcg[j] == 0 (metrics.py:79-82)
+ *    8 p, v       v = the largest label, p = the position of its first occurrence in score order
+ *    9 mrr[j]     1 / (p + 1) if p < ats[j], else 0
+ *   10 the reference's batch-wide mask, kept: if the v of ALL slates of the call add up to 0, every mrr of the call is 0
+ *                 (metrics.py:166-167 is one scalar for the batch).  So a slate without a relevant item inside a batch that has
+ *                 some keeps p = 0 and mrr = 1.
+ *   11 means      mean_out[m][j] = mean over the B slates of metric m (0 ndcg, 1 dcg, 2 mrr): an f64 sum in a fixed order,
+ *                 rounded once to f32
+ * The sums of 5 and 6 are accumulated in f64 and rounded once.  ndcg_out, dcg_out, mrr_out f32 [B, n_ats], each may be NULL;
+ * mean_out f32 [3, n_ats] or NULL; workspace: the bytes the sizing call names (0 for an unsupported shape), device.
+ * A bad config value, a NULL input, S > 4096 or B > 2^20: LTR_E_INVAL; a short workspace: LTR_E_NOMEM; nothing is launched and
+ * the checks never touch the device.  B * S == 0: LTR_OK, nothing is written.  Two launches on `stream` (one when mrr_out and
+ * mean_out are both NULL); no atomics, no memset, no allocation, no host sync: two calls give identical bits, dcg and ndcg of
+ * a slate do not depend on the other slates of the call, and the call can be captured into a graph. */
+typedef struct ltr_slate_metrics_config {
+  int32_t n_ats;        /* 1 .. 8 */
+  int32_t ats[8];       /* each >= 1; larger than S is allowed */
+  int32_t gain;         /* 0: 2^label - 1, 1: label */
+  float pad_value;      /* allrank PADDED_Y_VALUE -1 */
+  float filler_value;   /* ndcg where the ideal DCG is 0; allRank's 1.0 */
+} ltr_slate_metrics_config;
+size_t ltr_slate_metrics_workspace_bytes(int32_t B, int32_t S);
+int ltr_slate_metrics(const float* y_pred, const float* y_true, int32_t B, int32_t S, const ltr_slate_metrics_config* cfg,
+                      float* ndcg_out, float* dcg_out, float* mrr_out, float* mean_out, void* workspace, size_t ws_bytes,
+                      void* stream);
 
 /* The other half of SURVEY.md 8f-4: ONE optimisation step of the predictor's fine-tuning loop,
  * train/trainer.py:122-165 - forward of the OPTForSequenceClassification predictor on a slate of prompts

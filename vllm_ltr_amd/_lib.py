@@ -32,8 +32,9 @@ SYMBOLS = ("ltr_abi_version", "ltr_last_error", "ltr_create", "ltr_destroy", "lt
            "ltr_train_attention_workspace_bytes", "ltr_head_train_create", "ltr_head_train_create_encoder", "ltr_head_train_destroy",
            "ltr_head_train_workspace_bytes", "ltr_head_train_step", "ltr_head_train_read",
            "ltr_head_encoder_create", "ltr_head_encoder_destroy", "ltr_head_encoder_workspace_bytes",
-           "ltr_head_encoder_score", "ltr_lambdaloss", "ltr_lambdaloss_workspace_bytes")
-ABI_VERSION = 13
+           "ltr_head_encoder_score", "ltr_lambdaloss", "ltr_lambdaloss_workspace_bytes",
+           "ltr_slate_metrics", "ltr_slate_metrics_workspace_bytes")
+ABI_VERSION = 14
 
 
 LTR_E_INVAL, LTR_E_RANGE, LTR_E_NOMEM = -22, -34, -12
@@ -117,6 +118,15 @@ class OrderAgreementResult(C.Structure):
         ("max_gap_x", C.c_float), ("max_gap_y", C.c_float), ("gap_i", C.c_int32), ("gap_j", C.c_int32)]
 
 
+class SlateMetricsConfig(C.Structure):
+    """``ltr_slate_metrics_config``."""
+    _fields_ = [("n_ats", C.c_int32), ("ats", C.c_int32 * 8), ("gain", C.c_int32), ("pad_value", C.c_float),
+                ("filler_value", C.c_float)]
+
+
+SLATE_GAINS = {"pow2": 0, "identity": 1}
+
+
 class ProfileStats(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("work", C.c_double * 8), ("launches", C.c_int64 * 8)]
 
@@ -179,6 +189,9 @@ def _load() -> C.CDLL:
     lib.ltr_order_agreement_workspace_bytes.argtypes = [i64]
     lib.ltr_order_agreement_workspace_bytes.restype = sz
     lib.ltr_order_agreement.argtypes = [vp, vp, i32, vp, vp, sz, vp]
+    lib.ltr_slate_metrics_workspace_bytes.argtypes = [i32, i32]
+    lib.ltr_slate_metrics_workspace_bytes.restype = sz
+    lib.ltr_slate_metrics.argtypes = [vp, vp, i32, i32, C.POINTER(SlateMetricsConfig), vp, vp, vp, vp, vp, sz, vp]
     lib.ltr_head_create.argtypes = [C.POINTER(HeadDesc), C.POINTER(vp), i32, C.POINTER(vp)]
     lib.ltr_head_destroy.argtypes = [vp]
     lib.ltr_head_score.argtypes = [vp, vp, vp, i32, vp, vp]
@@ -213,7 +226,7 @@ def _load() -> C.CDLL:
                         "ltr_train_attention_workspace_bytes", "ltr_neuralndcg_workspace_bytes",
                         "ltr_order_agreement_workspace_bytes", "ltr_head_workspace_bytes",
                         "ltr_head_train_workspace_bytes", "ltr_head_encoder_workspace_bytes",
-                        "ltr_lambdaloss_workspace_bytes"):
+                        "ltr_lambdaloss_workspace_bytes", "ltr_slate_metrics_workspace_bytes"):
             fn.restype = C.c_int
     if lib.ltr_abi_version() != ABI_VERSION:
         raise LtrError(f"{LIB_PATH} has ABI version {lib.ltr_abi_version()}, this binding needs {ABI_VERSION}: rebuild")

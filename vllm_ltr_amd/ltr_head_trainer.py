@@ -98,7 +98,7 @@ class HipLTRHeadTrainer:
         self.lib = _lib.load()
         self.device = torch.device(device)
         self.n_features, self.fc_model, self.post_model, self.loss = n_features, fc_model, post_model, loss
-        self.transformer = transformer
+        self.transformer, self.pad_value = transformer, float(pad_value)
         sizes = list(fc_model["sizes"]) if fc_model else []
         norm = bool(fc_model and fc_model.get("input_norm"))
         if state is None:
@@ -222,3 +222,25 @@ class HipLTRHeadTrainer:
         else:
             pred = head.score(hidden)
         return metrics.kendall_tau(labels.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous(), pred)
+
+    def compute_metrics(self, hidden: torch.Tensor, labels: torch.Tensor, metrics: Dict[str, list],
+                        row_index: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> Dict[str, float]:
+        """allRank's epoch-end metrics of one batch (train_utils.py:48-72): ``{"ndcg": [5, 10], "mrr": [1]}`` ->
+        ``{"ndcg_5": .., "ndcg_10": .., "mrr_1": ..}``, the means over the B slates of the [B, S] labels (label ``pad_value``: a
+        padded item).  The scores are the current parameters', formed as in ``evaluate`` (a residual needs the batched path
+        and therefore fp16 weights) and ranked on the device (``metrics.slate_metrics``; its ``mrr`` keeps the reference's
+        batch-wide rule)."""
+        from .metrics import slate_metrics               # (the argument carries allRank's name and hides the module)
+        assert labels.dim() == 2
+        B, S = labels.shape
+        f32 = hidden.dtype == torch.float32 and not self.transformer and residual is None
+        head = self.to_head("f32" if f32 else "f16")
+        if self.transformer:
+            pred = head.score(hidden, row_index, residual, max_slate=S,
+                              cu_slates=torch.arange(0, B * S + 1, S, dtype=torch.int32, device=self.device))
+        else:
+            pred = head.score(hidden, row_index, residual)
+        if pred.numel() != B * S:
+            raise ValueError("HipLTRHeadTrainer.compute_metrics: labels [B, S] must name one scored row per item")
+        return slate_metrics(pred.view(B, S), labels.to(device=self.device, dtype=torch.float32).contiguous(), metrics,
+                             padding_indicator=self.pad_value)
